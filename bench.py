@@ -10,6 +10,12 @@ imgs/sec aggregate. Metric and config follow BASELINE.json
 Launch: `python bench.py --gpus N --steps K --warmup W`; for N>1 the driver
 uses torch.distributed.run with one rank per GPU over RCCL; we read
 RANK/LOCAL_RANK/WORLD_SIZE from the env. Weak scaling: per-GPU work fixed.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, print the result line. `--dump-outputs DIR` additionally writes
+what the last timed step produced (see dump_outputs). `--full` is where any
+measurement beyond the headline figure belongs (baselines, other precisions
+or sizes, per-kernel figures); there is none today, so it changes nothing.
 """
 
 from __future__ import annotations
@@ -19,6 +25,7 @@ import json
 import os
 import time
 
+import numpy as np
 import torch
 
 from dsin_amd import config as config_mod
@@ -49,6 +56,41 @@ def build_configs(args):
     return ae, pc
 
 
+DUMP_MAX_ELEMS = 4 * 1024 * 1024  # per array; 3 arrays of fp32 stay < 64 MB
+
+
+def _to_dump_array(t: torch.Tensor) -> np.ndarray:
+    a = t.detach().to(device="cpu", dtype=torch.float32).reshape(-1).numpy()
+    if a.size > DUMP_MAX_ELEMS:
+        # fixed, seeded sample: the same elements in every run and every build
+        idx = np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS,
+                                              replace=False)
+        idx.sort()
+        a = a[idx]
+    return np.ascontiguousarray(a)
+
+
+def dump_outputs(out_dir, last_out, model):
+    """Write what the last timed train step produced as DIR/<name>.npy
+    (float32): the (loss, bpp) pair train_step returns, and the parameters
+    the step left behind, flattened per optimizer group (AE and probclass).
+    Inputs and initial weights are seeded, so equal arguments give equal
+    inputs and two builds can be compared array for array."""
+    os.makedirs(out_dir, exist_ok=True)
+    loss, bpp = last_out
+    ae_params, pc_params = model.param_groups()
+    arrays = {
+        "loss_bpp": torch.stack([loss.detach().float().reshape(()),
+                                 bpp.detach().float().reshape(())]),
+        "params_ae": torch.cat([p.detach().float().reshape(-1)
+                                for p in ae_params]),
+        "params_pc": torch.cat([p.detach().float().reshape(-1)
+                                for p in pc_params]),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), _to_dump_array(t))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -64,6 +106,13 @@ def main():
     ap.add_argument("--device", type=str, default=None)
     ap.add_argument("--no-graph", action="store_true",
                     help="disable hipGraph capture of the train step")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's "
+                         "outputs (loss/bpp, updated parameters) as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline "
+                         "figure (none exist today)")
     # NOTE: no --channels-last flag. The custom conv/BN kernels are designed
     # around NCHW with K-contiguous gather tables; an NHWC input would be
     # silently re-laid-out at every op entry, so offering the flag would
@@ -108,10 +157,11 @@ def main():
 
     def step(i):
         x, y = batches[i % n_batches]
-        trainer.train_step(x, y if not args.ae_only else None)
+        return trainer.train_step(x, y if not args.ae_only else None)
 
+    last_out = None
     for i in range(args.warmup):
-        step(i)
+        last_out = step(i)
 
     def barrier_sync():
         if is_distributed():
@@ -122,9 +172,12 @@ def main():
     barrier_sync()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(args.warmup + i)
+        last_out = step(args.warmup + i)
     barrier_sync()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs and rank() == 0 and last_out is not None:
+        dump_outputs(args.dump_outputs, last_out, model)
 
     # which execution path actually ran (per-rank proof)
     import sys

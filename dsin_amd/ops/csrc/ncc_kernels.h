@@ -377,10 +377,14 @@ void ncc_main_v2_kernel(const ncbf16* __restrict__ tx,
     Pstat[4 * NCC_TP + tid] = ((float)(p % gw) + 0.5f) * (float)pw;
   }
 
-  // slice staging: 8 threads per patch row, each stages 64 taps (8 runs of
-  // 8 contiguous image elements via aoffs); zero-fills beyond K / beyond P
+  // slice staging: 8 threads per patch row, each stages NCC_SL/8 taps (runs
+  // of 8 contiguous image elements via aoffs); zero-fills beyond K / beyond
+  // P. The 8 threads must cover exactly NCC_SL taps: staging past the slice
+  // would spill into the next patch row, the other buffer and Pstat.
+  constexpr int S_TAPS = NCC_SL / 8;
+  static_assert(NCC_SL % 64 == 0, "slice = 8 threads x whole 8-tap runs");
   const int s_pi = tid & 31;
-  const int s_k0 = (tid >> 5) * 64;
+  const int s_k0 = (tid >> 5) * S_TAPS;
   const int sp = p0 + s_pi;
   const bool s_pok = sp < P;
   const long long s_pbase =
@@ -390,7 +394,7 @@ void ncc_main_v2_kernel(const ncbf16* __restrict__ tx,
   auto stage_slice = [&](int s0, int buf) {
     ncbf16* dst = As + buf * NCC_TP * ASTRIDE;
 #pragma unroll
-    for (int r8 = 0; r8 < 8; ++r8) {
+    for (int r8 = 0; r8 < S_TAPS / 8; ++r8) {
       const int kl = s_k0 + r8 * 8;
       const int kg = s0 + kl;
       u16x8 v = {};

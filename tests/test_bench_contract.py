@@ -33,6 +33,40 @@ def test_bench_single(tmp_path):
     _check_json(line, 1)
 
 
+def _run_dump(out_dir, extra=()):
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py")] + ARGS
+                       + ["--steps", "2", "--dump-outputs", str(out_dir)]
+                       + list(extra),
+                       cwd=REPO, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
+    rec = _check_json(line, 1)
+    assert rec["steps"] == 2 and rec["dtype"] == "fp32"
+    # ms_per_step is the time of ONE timed step: value = imgs / elapsed
+    assert abs(rec["ms_per_step"] * rec["value"] - 1000.0) < 1e-6 * 1000.0
+    import numpy as np
+    return {f: np.load(os.path.join(out_dir, f))
+            for f in sorted(os.listdir(out_dir))}
+
+
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's outputs as float .npy
+    files; equal arguments give equal inputs, so two runs (one with --full,
+    which must not change the timed path) agree array for array."""
+    import numpy as np
+    a = _run_dump(tmp_path / "a")
+    b = _run_dump(tmp_path / "b", extra=["--full"])
+    assert set(a) == {"loss_bpp.npy", "params_ae.npy", "params_pc.npy"}
+    assert set(a) == set(b)
+    assert sum(v.nbytes for v in a.values()) <= 64 * 1024 * 1024
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        assert a[name].size > 0 and np.isfinite(a[name]).all(), name
+        # fp32 CPU reference path: same inputs, same arithmetic
+        np.testing.assert_allclose(a[name], b[name], rtol=1e-5, atol=1e-6,
+                                   err_msg=name)
+
+
 def _run_distributed(n: int):
     import socket
     with socket.socket() as sock:  # pick a free rendezvous port
