@@ -240,6 +240,98 @@ def ncc_search(x_dec: torch.Tensor, y_dec: torch.Tensor, y_orig: torch.Tensor,
                               ph, pw, use_mask, l2lab=l2lab)
 
 
+# ---------------------------------------------------------------------------
+# MS-SSIM loss: one fused fp32 kernel per scale each way plus
+# the dyadic downsample. HIP kernels: csrc/msssim.hip.
+# ---------------------------------------------------------------------------
+
+SSIM_C1 = (0.01 * 255.0) ** 2
+SSIM_C2 = (0.03 * 255.0) ** 2
+SSIM_MAX_TAPS = 11
+
+
+def check_ssim_taps(ntaps: int, h: int, w: int, what: str = "ssim_scale"):
+    """The GPU kernels take an odd filter of at most 11 taps that fits the
+    image (the sizes the torch path accepts); anything else is a ValueError
+    raised before a kernel is launched."""
+    if ntaps % 2 == 0 or not 1 <= ntaps <= SSIM_MAX_TAPS:
+        raise ValueError(f"{what}: filter length {ntaps} must be odd and "
+                         f"<= {SSIM_MAX_TAPS}")
+    if ntaps > min(h, w):
+        raise ValueError(f"{what}: a {ntaps}-tap filter does not fit an "
+                         f"image of size {h}x{w}")
+
+
+class _SsimScaleFn(torch.autograd.Function):
+    """(mean ssim, mean cs) of one scale. Forward writes per-tile partial
+    sums; the ordered host-side sum makes the means bitwise deterministic.
+    Backward recomputes the blurred maps (nothing but the inputs is saved)."""
+
+    @staticmethod
+    def forward(ctx, a: torch.Tensor, b: torch.Tensor, taps: torch.Tensor,
+                c1: float, c2: float):
+        parts = _require_ext("ssim_scale_fwd")(a, b, taps, c1, c2)  # (2, S)
+        t = taps.numel()
+        n = a.shape[0] * a.shape[1] * (a.shape[2] - t + 1) * (a.shape[3] - t + 1)
+        means = (parts.sum(dim=1, dtype=torch.float64) / float(n)).float()
+        ctx.save_for_backward(a, b, taps)
+        ctx.c = (c1, c2)
+        ctx.set_materialize_grads(False)
+        return means[0], means[1]
+
+    @staticmethod
+    def backward(ctx, g_ssim, g_cs):
+        a, b, taps = ctx.saved_tensors
+        need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if (g_ssim is None and g_cs is None) or not (need_a or need_b):
+            return None, None, None, None, None
+        gs = g_ssim.float().contiguous() if g_ssim is not None else None
+        gc = g_cs.float().contiguous() if g_cs is not None else None
+        ga, gb = _require_ext("ssim_scale_bwd")(a, b, taps, gs, gc, ctx.c[0],
+                                                ctx.c[1], need_a, need_b)
+        return (ga if need_a else None, gb if need_b else None,
+                None, None, None)
+
+
+def ssim_scale(img1: torch.Tensor, img2: torch.Tensor, taps: torch.Tensor,
+               c1: float = SSIM_C1, c2: float = SSIM_C2
+               ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One MS-SSIM scale: (mean ssim, mean cs) of two NCHW images in 0..255
+    under the separable VALID blur with the 1-D filter `taps`.
+
+    GPU: fused fp32 kernels (inputs fp32 or bf16, fp32 scalars out), analytic
+    backward. CPU: the torch expression in the inputs' dtype."""
+    if img1.is_cuda:
+        check_ssim_taps(taps.numel(), img1.shape[2], img1.shape[3])
+        return _SsimScaleFn.apply(
+            img1.contiguous(), img2.contiguous(),
+            taps.to(device=img1.device, dtype=torch.float32).contiguous(),
+            float(c1), float(c2))
+    return ref.ssim_scale_ref(img1, img2, taps, c1, c2)
+
+
+class _Downsample2Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: torch.Tensor):
+        ctx.hw = (x.shape[2], x.shape[3])
+        ctx.bf16 = x.dtype == torch.bfloat16
+        return _require_ext("down2_fwd")(x)
+
+    @staticmethod
+    def backward(ctx, g: torch.Tensor):
+        return _require_ext("down2_bwd")(g.float().contiguous(), ctx.hw[0],
+                                         ctx.hw[1], ctx.bf16)
+
+
+def downsample2(x: torch.Tensor) -> torch.Tensor:
+    """MS-SSIM dyadic downsample (N,C,H,W) -> (N,C,ceil(H/2),ceil(W/2)):
+    REFLECT pad of one row/column at the end, 2-tap box filter, ::2.
+    GPU: one kernel each way, fp32 out (fp32 or bf16 in). CPU: torch."""
+    if x.is_cuda:
+        return _Downsample2Fn.apply(x.contiguous())
+    return ref.downsample2_ref(x)
+
+
 # re-exports used across the package
 kitti_normalize = ref.kitti_normalize
 kitti_denormalize = ref.kitti_denormalize

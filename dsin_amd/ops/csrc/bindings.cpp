@@ -62,6 +62,14 @@ std::vector<torch::Tensor> l1_bwd(torch::Tensor x, torch::Tensor y,
 torch::Tensor hterms_part(torch::Tensor bc, torch::Tensor heat);
 std::vector<torch::Tensor> hterms_bwd(torch::Tensor bc, torch::Tensor heat,
                                       torch::Tensor g2, bool need_gheat);
+torch::Tensor ssim_scale_fwd(torch::Tensor a, torch::Tensor b,
+                             torch::Tensor taps, double c1, double c2);
+std::vector<torch::Tensor> ssim_scale_bwd(
+    torch::Tensor a, torch::Tensor b, torch::Tensor taps,
+    c10::optional<torch::Tensor> g_ssim, c10::optional<torch::Tensor> g_cs,
+    double c1, double c2, bool need_ga, bool need_gb);
+torch::Tensor down2_fwd(torch::Tensor x);
+torch::Tensor down2_bwd(torch::Tensor g, int64_t H, int64_t W, bool bf16_out);
 }  // namespace dsin
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -94,4 +102,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hterms_part", &dsin::hterms_part,
         "fused (sum bc, sum bc*heatmap) partials");
   m.def("hterms_bwd", &dsin::hterms_bwd, "rate-term backward");
+  m.def("ssim_scale_fwd", &dsin::ssim_scale_fwd,
+        "fused one-scale SSIM/CS partial sums (fp32)");
+  m.def("ssim_scale_bwd", &dsin::ssim_scale_bwd,
+        "one-scale SSIM/CS analytic gradient");
+  m.def("down2_fwd", &dsin::down2_fwd, "MS-SSIM dyadic downsample");
+  m.def("down2_bwd", &dsin::down2_bwd, "MS-SSIM dyadic downsample adjoint");
 }

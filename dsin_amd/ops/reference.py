@@ -22,6 +22,8 @@ __all__ = [
     "kitti_normalize",
     "kitti_denormalize",
     "bitcost_ce_ref",
+    "ssim_scale_ref",
+    "downsample2_ref",
     "pad_for_probclass_ref",
     "ncc_search_ref",
     "assemble_patches",
@@ -130,6 +132,49 @@ def bitcost_ce_ref(logits: torch.Tensor, symbols: torch.Tensor) -> torch.Tensor:
     (reference src/probclass_imgcomp.py:100-106).
     """
     return F.cross_entropy(logits, symbols, reduction="none") * LOG2_E
+
+
+# ---------------------------------------------------------------------------
+# MS-SSIM building blocks (reference src/ms_ssim_imgcomp.py:16-64,81-112):
+# one scale's (ssim, cs) means for given Gaussian taps, and the dyadic
+# downsample between scales.
+# ---------------------------------------------------------------------------
+
+def _conv_valid(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """Per-channel VALID conv with one shared (1, 1, kh, kw) filter."""
+    c = x.shape[1]
+    return F.conv2d(x, w.expand(c, 1, w.shape[2], w.shape[3]), groups=c)
+
+
+def blur_sep_ref(x: torch.Tensor, k1d: torch.Tensor) -> torch.Tensor:
+    """Per-channel separable VALID conv, rows then cols (reference :31-42)."""
+    x = _conv_valid(x, k1d.view(1, 1, 1, -1))
+    return _conv_valid(x, k1d.view(1, 1, -1, 1))
+
+
+def ssim_scale_ref(img1: torch.Tensor, img2: torch.Tensor, taps: torch.Tensor,
+                   c1: float, c2: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(mean ssim, mean cs) of one scale; taps is the 1-D Gaussian."""
+    mu1 = blur_sep_ref(img1, taps)
+    mu2 = blur_sep_ref(img2, taps)
+    s11 = blur_sep_ref(img1 * img1, taps) - mu1 * mu1
+    s22 = blur_sep_ref(img2 * img2, taps) - mu2 * mu2
+    s12 = blur_sep_ref(img1 * img2, taps) - mu1 * mu2
+    v1 = 2.0 * s12 + c2
+    v2 = s11 + s22 + c2
+    ssim = (((2.0 * mu1 * mu2 + c1) * v1) / ((mu1 * mu1 + mu2 * mu2 + c1) * v2)).mean()
+    cs = (v1 / v2).mean()
+    return ssim, cs
+
+
+def downsample2_ref(x: torch.Tensor) -> torch.Tensor:
+    """2-tap box filter, REFLECT pad (0 front, 1 back), separable (width then
+    height), then ::2 (reference kernel_blur at :46-64 with pad_w1=0,
+    pad_w2=1)."""
+    x = F.pad(x, (0, 1, 0, 1), mode="reflect")
+    x = _conv_valid(x, x.new_full((1, 1, 1, 2), 0.5))
+    x = _conv_valid(x, x.new_full((1, 1, 2, 1), 0.5))
+    return x[:, :, ::2, ::2]
 
 
 # ---------------------------------------------------------------------------
