@@ -222,6 +222,26 @@ def bitcost_ce(logits: torch.Tensor, symbols: torch.Tensor) -> torch.Tensor:
 # materializes the (P, Hc, Wc) correlation volume or the Gaussian mask.
 # ---------------------------------------------------------------------------
 
+def check_ncc_inputs(x_dec, y_dec, y_orig, ph: int, pw: int, use_mask: bool):
+    """Inputs both devices accept, checked before anything is launched."""
+    if x_dec.dim() != 3 or x_dec.shape[0] != 3:
+        raise ValueError(f"ncc_search: images must be (3, H, W), got "
+                         f"{tuple(x_dec.shape)}")
+    if x_dec.shape != y_dec.shape or x_dec.shape != y_orig.shape:
+        raise ValueError(
+            f"ncc_search: the three images must share one shape, got "
+            f"{tuple(x_dec.shape)}, {tuple(y_dec.shape)}, "
+            f"{tuple(y_orig.shape)}")
+    h, w = x_dec.shape[1], x_dec.shape[2]
+    if ph < 1 or pw < 1 or h % ph or w % pw:
+        raise ValueError(f"ncc_search: a {h}x{w} image does not tile by "
+                         f"{ph}x{pw} patches")
+    if use_mask and (ph % 2 or pw % 2):
+        raise ValueError(
+            f"ncc_search: the location prior is defined only for even patch "
+            f"sizes, got {ph}x{pw} (pass use_mask=False)")
+
+
 @torch.no_grad()
 def ncc_search(x_dec: torch.Tensor, y_dec: torch.Tensor, y_orig: torch.Tensor,
                ph: int, pw: int, use_mask: bool = True, l2lab: bool = False
@@ -231,6 +251,7 @@ def ncc_search(x_dec: torch.Tensor, y_dec: torch.Tensor, y_orig: torch.Tensor,
     argmin of squared L2) — served by the torch path on every device; the
     streaming HIP kernel covers the Pearson+H1H2H3 mode of the shipped
     configs."""
+    check_ncc_inputs(x_dec, y_dec, y_orig, ph, pw, use_mask)
     if x_dec.is_cuda and not l2lab:
         fn = _require_ext("ncc_search")
         y_syn, rows, cols = fn(x_dec.contiguous().float(), y_dec.contiguous().float(),

@@ -113,6 +113,14 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search(
                        (unsigned long long*)best.data_ptr(), H, W, ph, pw,
                        gw, P, Hc, Wc, use_mask ? 1 : 0);
   }
+  // a refused launch (e.g. the dynamic LDS request) would leave `best` zero,
+  // and scatter_kernel would decode index 0xFFFFFFFF from it
+  {
+    const hipError_t err = hipGetLastError();
+    TORCH_CHECK(err == hipSuccess, "ncc_search: launch of ",
+                v2 ? "ncc_main_v2_kernel" : "ncc_main_kernel", " with ", lds,
+                " bytes of dynamic LDS failed: ", hipGetErrorString(err));
+  }
 
   auto y_syn = torch::empty_like(y_orig);
   auto rows = torch::empty({P}, optsF.dtype(torch::kInt64));

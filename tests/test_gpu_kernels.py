@@ -523,7 +523,9 @@ def test_graph_capture_matches_eager(dev):
     for x, y in seq:
         loss_e, _ = tr2.train_step(x, y)
         le = float(loss_e)
-    # wrw fp32 atomics make runs non-bitwise; trajectories must still track
+    # no kernel accumulates with fp32 atomics any more (see
+    # test_step_bitwise_determinism); the bound dates from when wrw did and
+    # is kept as it was: the trajectories must track
     assert abs(lg2 - le) / max(abs(le), 1.0) < 0.03, (lg, lg2, le)
 
 
@@ -563,7 +565,8 @@ def test_checkpoint_roundtrip_fused_adam(dev, tmp_path):
     step = checkpoint.load(model2, [tr2.opt_ae, tr2.opt_pc], p, ae)
     tr2.global_step = step
     tr2.train_step(*batches[2])
-    # bn_bwd's fp32 atomics make per-run rounding order nondeterministic;
-    # tolerance covers one optimizer step of that jitter
+    # the reductions are ordered sums now (no fp32 atomics, see
+    # test_step_bitwise_determinism); the tolerance dates from when bn_bwd
+    # accumulated with atomics and is kept as it was
     torch.testing.assert_close(model2.encoder.h1.conv.weight, w_ref,
                                rtol=1e-4, atol=1e-5)
