@@ -1,0 +1,168 @@
+"""Image <-> bytes: the container around the entropy-coded symbol volume.
+
+    data = compress(model, x)               # x: (3,H,W) or (1,3,H,W), 0..255
+    x_dec, x_with_si = decompress(model, data, y)
+
+Both run the model in eval mode, as ``DSIN.reconstruct`` does, and produce
+the same ``x_dec`` / ``x_with_si`` as ``reconstruct`` under the same autocast
+setting: the decoder input is ``centers[symbols]``, which is what the
+quantizer's ``qbar`` equals.
+
+Container (little-endian, 22-byte header, then the payload):
+
+    4s  magic  b"DSIN"
+    B   version (1)
+    B   backend id (0 torch, 1 hip)
+    H   C   bottleneck channels
+    H   Hb  bottleneck height
+    H   Wb  bottleneck width
+    H   L   number of centers
+    I   CRC32 of the probclass weights, biases and the centers (fp32 bytes)
+    I   payload length in bytes
+    ..  payload: range-coded symbols in wave order
+
+The backend is hip when the model is on a GPU and torch on the CPU. The two
+do NOT decode each other's streams: the hip kernels evaluate the context
+model in fp32 with their own ``expf`` and scale tables by 65536-L, the torch
+path uses the torch convs (bf16 panels on a GPU) and a 65536 scale, so the
+frequency tables differ. A stream records its backend and ``decompress``
+refuses one it cannot reproduce.
+"""
+
+from __future__ import annotations
+
+import struct
+import zlib
+from typing import Optional, Tuple
+
+import torch
+
+from .entropy import decode_symbols, encode_symbols
+
+MAGIC = b"DSIN"
+VERSION = 1
+BACKEND_IDS = {"torch": 0, "hip": 1}
+_HEADER = struct.Struct("<4sBBHHHHII")
+HEADER_SIZE = _HEADER.size
+
+
+def model_backend(model) -> str:
+    """hip on a GPU, torch on the CPU."""
+    dev = model.encoder.quantizer.centers.device
+    return "hip" if dev.type == "cuda" else "torch"
+
+
+def probclass_crc(model) -> int:
+    """CRC32 over the fp32 bytes of every probclass weight and bias (layer
+    order conv0, res_conv1, res_conv2, conv2) and of the centers."""
+    pc = model.probclass
+    crc = 0
+    tensors = []
+    for m in (pc.conv0, pc.res_conv1, pc.res_conv2, pc.conv2):
+        tensors += [m.weight, m.bias]
+    tensors.append(model.encoder.quantizer.centers)
+    for t in tensors:
+        raw = t.detach().float().cpu().contiguous().numpy().tobytes()
+        crc = zlib.crc32(raw, crc)
+    return crc & 0xFFFFFFFF
+
+
+def pack_container(backend: str, shape, L: int, crc: int,
+                   payload: bytes) -> bytes:
+    C, Hb, Wb = (int(v) for v in shape)
+    if max(C, Hb, Wb, L) > 0xFFFF:
+        raise ValueError(f"container: dimension too large in {shape}, L={L}")
+    return _HEADER.pack(MAGIC, VERSION, BACKEND_IDS[backend], C, Hb, Wb,
+                        int(L), crc, len(payload)) + payload
+
+
+def parse_container(data: bytes):
+    """-> (backend id, (C, Hb, Wb), L, crc, payload). ValueError on a bad
+    magic or version or a truncated stream."""
+    if len(data) < HEADER_SIZE:
+        raise ValueError(f"container: {len(data)} bytes is shorter than the "
+                         f"{HEADER_SIZE}-byte header")
+    magic, ver, bid, C, Hb, Wb, L, crc, n = _HEADER.unpack_from(data)
+    if magic != MAGIC:
+        raise ValueError(f"container: bad magic {magic!r}")
+    if ver != VERSION:
+        raise ValueError(f"container: version {ver}, this build reads "
+                         f"{VERSION}")
+    if bid not in BACKEND_IDS.values():
+        raise ValueError(f"container: unknown backend id {bid}")
+    if min(C, Hb, Wb, L) < 1:
+        raise ValueError(f"container: empty volume {(C, Hb, Wb)}, L={L}")
+    payload = data[HEADER_SIZE:HEADER_SIZE + n]
+    if len(payload) != n:
+        raise ValueError(f"container: payload truncated, header says {n} "
+                         f"bytes, {len(payload)} present")
+    return bid, (C, Hb, Wb), L, crc, payload
+
+
+def _as_batch(x: torch.Tensor, what: str) -> torch.Tensor:
+    if x.dim() == 3:
+        x = x.unsqueeze(0)
+    if x.dim() != 4 or x.shape[0] != 1 or x.shape[1] != 3:
+        raise ValueError(f"{what} must be (3,H,W) or (1,3,H,W), got "
+                         f"{tuple(x.shape)}")
+    return x
+
+
+@torch.no_grad()
+def compress(model, x: torch.Tensor) -> bytes:
+    """Encode one image to a self-describing byte string."""
+    from ..ops import conv as _conv
+    x = _as_batch(x, "x")
+    _conv.begin_step()
+    model.eval()
+    z = model.encoder(x)
+    symbols = z.symbols[0]
+    centers = model.encoder.quantizer.centers.detach()
+    backend = model_backend(model)
+    payload = encode_symbols(model.probclass, centers, symbols,
+                             backend=backend)
+    return pack_container(backend, symbols.shape, centers.numel(),
+                          probclass_crc(model), payload)
+
+
+@torch.no_grad()
+def decompress(model, data: bytes, y: Optional[torch.Tensor] = None
+               ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """-> (x_dec, x_with_si). x_with_si is None without a side image y or
+    for an AE-only model. Every header problem is a ValueError raised
+    before any network or kernel runs."""
+    from .. import ops
+    from ..ops import conv as _conv
+    bid, shape, L, crc, payload = parse_container(data)
+    backend = model_backend(model)
+    if bid != BACKEND_IDS[backend]:
+        names = {v: k for k, v in BACKEND_IDS.items()}
+        raise ValueError(
+            f"container: stream was written by the {names[bid]} backend, "
+            f"this model runs the {backend} backend (hip on a GPU, torch on "
+            f"the CPU); the two do not decode each other's streams")
+    centers = model.encoder.quantizer.centers.detach()
+    if L != centers.numel():
+        raise ValueError(f"container: stream has L={L}, the model has "
+                         f"{centers.numel()} centers")
+    if shape[0] != int(model.ae_config.num_chan_bn):
+        raise ValueError(f"container: stream has {shape[0]} channels, the "
+                         f"model has {model.ae_config.num_chan_bn}")
+    if crc != probclass_crc(model):
+        raise ValueError("container: CRC mismatch, the stream was written "
+                         "with other probclass weights or centers")
+    if y is not None:
+        y = _as_batch(y, "y")
+    _conv.begin_step()
+    model.eval()
+    symbols = decode_symbols(model.probclass, centers, payload, shape,
+                             device=centers.device, backend=backend)
+    qbar = centers.float()[symbols].unsqueeze(0)
+    x_dec = model.decoder(qbar)
+    if y is None or model.ae_only:
+        return x_dec, None
+    y_dec = model.create_y_dec(y)
+    y_syn = model.sifinder(x_dec.float(), y.float(), y_dec.float())
+    cat = torch.cat([ops.kitti_normalize(x_dec),
+                     ops.kitti_normalize(y_syn.to(x_dec.dtype))], dim=1)
+    return x_dec, ops.kitti_denormalize(model.sinet(cat))

@@ -135,10 +135,68 @@ def _gather_blocks(q_pad: torch.Tensor, wave: np.ndarray,
     return torch.stack(blocks)
 
 
+BACKENDS = ("torch", "hip")
+
+
+def _check_backend(backend: str) -> None:
+    if backend not in BACKENDS:
+        raise ValueError(f"backend must be one of {BACKENDS}, got {backend!r}")
+
+
+def _torch_backend_cache_reset(device: torch.device) -> None:
+    """The torch backend on a GPU runs four masked convs per wave, each on a
+    fresh weight*mask temporary that the W-panel cache would pin; drop the
+    cache around a call so a decode does not grow it without bound."""
+    if device.type == "cuda":
+        from ..ops import conv as _conv
+        _conv.begin_step()
+
+
+def _hip_setup(pc: ProbClass, centers: torch.Tensor, shape, device):
+    """Checks + the pad-filled value buffer, wave-ordered positions and wave
+    offsets shared by the hip encoder and decoder."""
+    from .. import ops
+    ops.check_pc_shape(pc)
+    if device.type != "cuda":
+        raise ValueError("backend='hip' needs the model and symbols on a GPU")
+    C, H, W = (int(v) for v in shape)
+    if min(C, H, W) < 1:
+        raise ValueError(f"backend='hip': empty symbol volume {shape}")
+    pad = pc.context_size() // 2
+    waves = _wave_order(C, H, W, pad)
+    pos = torch.from_numpy(np.concatenate(waves).astype(np.int32)).to(device)
+    offsets = np.concatenate([[0], np.cumsum([len(w) for w in waves])])
+    q_pad = torch.full((C + pad, H + 2 * pad, W + 2 * pad),
+                       float(_pad_value(pc, centers)),
+                       dtype=torch.float32, device=device)
+    return ops, pad, pos, offsets, q_pad
+
+
+def _encode_symbols_hip(pc, centers, symbols) -> bytes:
+    dev = centers.device
+    ops, pad, pos, _, q_pad = _hip_setup(pc, centers, symbols.shape, dev)
+    sym = symbols.to(dev)
+    C, H, W = sym.shape
+    q_pad[pad:, pad:H + pad, pad:W + pad] = centers.float()[sym]
+    p = pos.long()
+    return ops.pc_encode(pc, q_pad, pos, sym[p[:, 0], p[:, 1], p[:, 2]])
+
+
+def _decode_symbols_hip(pc, centers, data, shape, device) -> torch.Tensor:
+    ops, _, pos, offsets, q_pad = _hip_setup(pc, centers, shape, device)
+    return ops.pc_decode(pc, q_pad, pos, offsets, data, centers)
+
+
 @torch.no_grad()
 def encode_symbols(pc: ProbClass, centers: torch.Tensor,
-                   symbols: torch.Tensor) -> bytes:
+                   symbols: torch.Tensor, backend: str = "torch") -> bytes:
     """symbols: (C, H, W) int64 -> range-coded byte stream, wave order.
+
+    backend="torch" (default): the per-wave torch path below, on any device.
+    backend="hip": the device-resident codec (ops.pc_encode; GPU only). The
+    two backends do not decode each other's streams: their tables differ
+    (fp32 kernels and a 65536-L table scale against the torch convs and a
+    65536 scale).
 
     Frequencies are computed through the SAME per-wave batched network
     calls the decoder runs — same batch shapes, same block contents at
@@ -148,6 +206,9 @@ def encode_symbols(pc: ProbClass, centers: torch.Tensor,
     backend — different reduction shapes — and was removed: a codec whose
     streams sometimes fail to decode is worse than no fast path.)
     """
+    _check_backend(backend)
+    if backend == "hip":
+        return _encode_symbols_hip(pc, centers, symbols)
     sym = symbols.cpu().numpy()
     C, H, W = sym.shape
     pad = pc.context_size() // 2
@@ -155,6 +216,7 @@ def encode_symbols(pc: ProbClass, centers: torch.Tensor,
     enc = RangeEncoder()
     pred = PredictionNetwork(pc, centers)
     dev = centers.device
+    _torch_backend_cache_reset(dev)
     # ground-truth value buffer: causal reads see the same values the
     # decoder will have reconstructed; non-causal positions hold ground
     # truth here vs the pad value on the decoder side, but every non-causal
@@ -171,19 +233,26 @@ def encode_symbols(pc: ProbClass, centers: torch.Tensor,
             cum = _cumulate(f)
             s = int(sym[c, h, w])
             enc.encode(int(cum[s]), int(f[s]), int(cum[-1]))
+    _torch_backend_cache_reset(dev)
     return enc.finish()
 
 
 @torch.no_grad()
 def decode_symbols(pc: ProbClass, centers: torch.Tensor, data: bytes,
                    shape: Tuple[int, int, int],
-                   device: Optional[torch.device] = None) -> torch.Tensor:
+                   device: Optional[torch.device] = None,
+                   backend: str = "torch") -> torch.Tensor:
     """Wavefront autoregressive decode of a (C, H, W) symbol volume. Exact
-    inverse of encode_symbols: one batched network call per skewed wave
-    (O(25C + 5H + W) calls), then the wave's symbols are range-decoded
-    sequentially against the batch's frequency tables."""
+    inverse of encode_symbols with the same backend: one batched network
+    call per skewed wave (O(25C + 5H + W) calls), then the wave's symbols
+    are range-decoded sequentially against the batch's frequency tables.
+    backend="hip" keeps both steps on the GPU (ops.pc_decode)."""
+    _check_backend(backend)
     C, H, W = shape
-    device = device or centers.device
+    device = torch.device(device or centers.device)
+    if backend == "hip":
+        return _decode_symbols_hip(pc, centers, data, shape, device)
+    _torch_backend_cache_reset(device)
     pred = PredictionNetwork(pc, centers)
     pad = pc.context_size() // 2
     Dc, Hc, Wc = pad + 1, 2 * pad + 1, 2 * pad + 1
@@ -203,4 +272,5 @@ def decode_symbols(pc: ProbClass, centers: torch.Tensor, data: bytes,
             dec.decode_update(int(cum[s]), int(f[s]), tot)
             out[c, h, w] = s
             q_pad[c + Dc - 1, h + pad, w + pad] = float(centers_f[s])
+    _torch_backend_cache_reset(device)
     return out.to(device)

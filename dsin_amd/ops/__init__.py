@@ -353,6 +353,159 @@ def downsample2(x: torch.Tensor) -> torch.Tensor:
     return ref.downsample2_ref(x)
 
 
+# ---------------------------------------------------------------------------
+# Entropy codec: per-position probclass context model + device range coder.
+# HIP kernels: csrc/pc_codec.hip (step functions in csrc/rc_coder.h).
+# ---------------------------------------------------------------------------
+
+PC_MAX_K = 32
+PC_MAX_L = 16
+PC_FREQ_SCALE = 1 << 16
+
+
+def pc_live_taps(mask: torch.Tensor) -> torch.Tensor:
+    """Flattened (d, kh, kw) indices of the taps a causality mask keeps."""
+    return torch.nonzero(mask.reshape(-1), as_tuple=False).reshape(-1)
+
+
+def check_pc_shape(pc) -> Tuple[int, int]:
+    """(k, L) of a ProbClass the codec kernels serve; ValueError otherwise,
+    before anything is launched."""
+    k, L = int(pc.conv0.weight.shape[0]), int(pc.L)
+    if int(pc.K) != 3:
+        raise ValueError(f"pc codec: kernel_size must be 3, got {pc.K}")
+    if not 1 <= k <= PC_MAX_K:
+        raise ValueError(f"pc codec: k={k} outside [1, {PC_MAX_K}]")
+    if not 2 <= L <= PC_MAX_L:
+        raise ValueError(f"pc codec: L={L} outside [2, {PC_MAX_L}]")
+    return k, L
+
+
+@torch.no_grad()
+def pc_pack_weights(pc) -> torch.Tensor:
+    """Flat fp32 buffer of the four masked convs with the masked taps
+    dropped by index: per layer w[tap][ci][co] over the live taps (13 for
+    first_mask, 14 for other_mask) followed by the bias. Output channels of
+    the three k-wide layers are zero-padded to a multiple of 8; conv2 keeps
+    its L outputs. Layout documented in csrc/pc_codec.hip."""
+    k, _ = check_pc_shape(pc)
+    kp = (k + 7) // 8 * 8
+    parts = []
+    for conv, cop in ((pc.conv0, kp), (pc.res_conv1, kp),
+                      (pc.res_conv2, kp), (pc.conv2, None)):
+        w = conv.weight.detach().float()
+        co, ci = w.shape[0], w.shape[1]
+        live = pc_live_taps(conv.mask).to(w.device)
+        wl = w.reshape(co, ci, -1)[:, :, live].permute(2, 1, 0)  # tap,ci,co
+        b = conv.bias.detach().float()
+        if cop is not None and cop != co:
+            wl = torch.nn.functional.pad(wl, (0, cop - co))
+            b = torch.nn.functional.pad(b, (0, cop - co))
+        parts += [wl.reshape(-1), b]
+    return torch.cat(parts).contiguous()
+
+
+def pc_logits_packed_ref(packed: torch.Tensor, k: int, L: int,
+                         ctx: torch.Tensor) -> torch.Tensor:
+    """Torch evaluation of one (5, 9, 9) context from the packed layout, in
+    the dtype of `packed`: what the pc_freqs kernel computes per position
+    (same live taps, same layer order), used to test the packing."""
+    kp = (k + 7) // 8 * 8
+    ctx = ctx.to(packed.dtype)
+
+    off = [0]
+
+    def take(n):
+        t = packed[off[0]:off[0] + n]
+        off[0] += n
+        return t
+
+    def layer(x, nt, cin, cop):
+        # x: (cin, D, H, W) -> (cop, D-1, H-2, W-2) over the first nt taps
+        w = take(nt * cin * cop).reshape(nt, cin, cop)
+        b = take(cop)
+        D, H, W = x.shape[1] - 1, x.shape[2] - 2, x.shape[3] - 2
+        out = b.reshape(cop, 1, 1, 1).expand(cop, D, H, W).clone()
+        for t in range(nt):
+            d, y, z = t // 9, (t % 9) // 3, t % 3
+            win = x[:cin, d:d + D, y:y + H, z:z + W]
+            out = out + torch.einsum("idhw,io->odhw", win, w[t])
+        return out
+
+    a0 = torch.relu(layer(ctx.reshape(1, 5, 9, 9), 13, 1, kp))
+    a1 = torch.relu(layer(a0, 14, k, kp))
+    a2 = layer(a1, 14, k, kp) + a0[:, 2:, 2:-2, 2:-2]
+    return layer(a2, 14, k, L).reshape(L)
+
+
+def pc_table_from_probs(p: torch.Tensor) -> torch.Tensor:
+    """The hip backend's table rule on fp32 probability rows (n, L):
+    f = max(1, floor(p * (65536 - L))), so tot <= 65535."""
+    L = p.shape[-1]
+    return torch.floor(p.float() * float(PC_FREQ_SCALE - L)).to(
+        torch.int32).clamp(min=1)
+
+
+def _pc_args(pc, q_pad: torch.Tensor, pos: torch.Tensor):
+    k, L = check_pc_shape(pc)
+    if not q_pad.is_cuda:
+        raise ValueError("pc codec: the hip backend needs GPU tensors")
+    if q_pad.dim() != 3 or min(q_pad.shape[0] - 4, q_pad.shape[1] - 8,
+                               q_pad.shape[2] - 8) < 1:
+        raise ValueError(f"pc codec: q_pad must be (C+4, H+8, W+8), got "
+                         f"{tuple(q_pad.shape)}")
+    if pos.dim() != 2 or pos.shape[1] != 3:
+        raise ValueError("pc codec: positions must be (n, 3)")
+    return (k, L, q_pad.float().contiguous(),
+            pos.to(device=q_pad.device, dtype=torch.int32).contiguous())
+
+
+@torch.no_grad()
+def pc_freqs(pc, q_pad: torch.Tensor, pos: torch.Tensor,
+             packed: Optional[torch.Tensor] = None
+             ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Context model at a list of positions of the padded value buffer:
+    (fp32 logits (n, L), int32 frequency tables (n, L)). GPU only."""
+    k, L, q_pad, pos = _pc_args(pc, q_pad, pos)
+    fn = _require_ext("pc_freqs")
+    if packed is None:
+        packed = pc_pack_weights(pc)
+    return fn(q_pad, pos, packed, k, L)
+
+
+@torch.no_grad()
+def pc_encode(pc, q_pad: torch.Tensor, pos: torch.Tensor,
+              symbols: torch.Tensor) -> bytes:
+    """Range-code symbols (n,) at positions (n, 3) in the given order: one
+    pc_freqs launch, one rc_encode launch, one device-to-host copy."""
+    k, L, q_pad, pos = _pc_args(pc, q_pad, pos)
+    fn = _require_ext("pc_encode")
+    syms = symbols.to(device=q_pad.device, dtype=torch.int32).contiguous()
+    buf = fn(q_pad, pos, syms, pc_pack_weights(pc), k, L).cpu().numpy()
+    n = int.from_bytes(buf[:8].tobytes(), "little")
+    if n > buf.size - 8:
+        raise RuntimeError(f"pc_encode: stream of {n} bytes overran the "
+                           f"{buf.size - 8}-byte device buffer")
+    return buf[8:8 + n].tobytes()
+
+
+@torch.no_grad()
+def pc_decode(pc, q_pad: torch.Tensor, pos: torch.Tensor, offsets,
+              data: bytes, centers: torch.Tensor) -> torch.Tensor:
+    """Wavefront decode: wave i is pos[offsets[i]:offsets[i+1]]. q_pad is
+    filled in place with centers[symbol]; returns (C, H, W) int64 symbols.
+    The wave loop runs in C++ (two launches per wave, no host sync)."""
+    k, L, q_pad_c, pos = _pc_args(pc, q_pad, pos)
+    if q_pad_c.data_ptr() != q_pad.data_ptr():
+        raise ValueError("pc_decode: q_pad must be fp32 and contiguous")
+    fn = _require_ext("pc_decode")
+    raw = torch.frombuffer(bytearray(data) if len(data) else bytearray(1),
+                           dtype=torch.uint8)[:len(data)]
+    return fn(q_pad, pos, [int(o) for o in offsets], pc_pack_weights(pc), k,
+              L, raw.to(q_pad.device).contiguous(),
+              centers.detach().to(q_pad.device).float().contiguous())
+
+
 # re-exports used across the package
 kitti_normalize = ref.kitti_normalize
 kitti_denormalize = ref.kitti_denormalize

@@ -70,6 +70,21 @@ std::vector<torch::Tensor> ssim_scale_bwd(
     double c1, double c2, bool need_ga, bool need_gb);
 torch::Tensor down2_fwd(torch::Tensor x);
 torch::Tensor down2_bwd(torch::Tensor g, int64_t H, int64_t W, bool bf16_out);
+std::tuple<torch::Tensor, torch::Tensor> pc_freqs(torch::Tensor q_pad,
+                                                  torch::Tensor pos,
+                                                  torch::Tensor wts, int64_t k,
+                                                  int64_t L);
+torch::Tensor rc_encode(torch::Tensor syms, torch::Tensor freqs);
+torch::Tensor rc_decode(torch::Tensor data, torch::Tensor freqs);
+torch::Tensor pc_encode(torch::Tensor q_pad, torch::Tensor pos,
+                        torch::Tensor syms, torch::Tensor wts, int64_t k,
+                        int64_t L);
+torch::Tensor pc_decode(torch::Tensor q_pad, torch::Tensor pos,
+                        std::vector<int64_t> offsets, torch::Tensor wts,
+                        int64_t k, int64_t L, torch::Tensor data,
+                        torch::Tensor centers);
+torch::Tensor rc_encode_host(torch::Tensor syms, torch::Tensor freqs);
+torch::Tensor rc_decode_host(torch::Tensor data, torch::Tensor freqs);
 }  // namespace dsin
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -108,4 +123,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "one-scale SSIM/CS analytic gradient");
   m.def("down2_fwd", &dsin::down2_fwd, "MS-SSIM dyadic downsample");
   m.def("down2_bwd", &dsin::down2_bwd, "MS-SSIM dyadic downsample adjoint");
+  m.def("pc_freqs", &dsin::pc_freqs,
+        "probclass context model per position: (logits, frequency tables)");
+  m.def("rc_encode", &dsin::rc_encode, "device range encoder");
+  m.def("rc_decode", &dsin::rc_decode, "device range decoder, given tables");
+  m.def("pc_encode", &dsin::pc_encode, "context model + range encoder");
+  m.def("pc_decode", &dsin::pc_decode, "wavefront context-model decoder");
+  m.def("rc_encode_host", &dsin::rc_encode_host,
+        "host build of the range-encoder step functions");
+  m.def("rc_decode_host", &dsin::rc_decode_host,
+        "host build of the range-decoder step functions");
 }

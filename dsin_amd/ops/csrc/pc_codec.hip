@@ -1,0 +1,531 @@
+// Device-resident entropy codec: the probclass context model evaluated per
+// position (pc_freqs) and a range coder that never leaves the GPU
+// (rc_encode / rc_decode_wave).
+//
+// pc_freqs: one workgroup per queried position (c, h, w). The position's
+// 5x9x9 causal context is read from the padded value buffer q_pad
+// (C+4, H+8, W+8) and pushed through the four masked VALID 3-D convs in the
+// order ProbClass.logits uses:
+//   conv0 +ReLU  1 -> k   5x9x9 -> 4x7x7
+//   res_conv1 +ReLU k -> k 4x7x7 -> 3x5x5
+//   res_conv2 + conv0[:, 2:, 2:-2, 2:-2]   3x5x5 -> 2x3x3
+//   conv2  k -> L          2x3x3 -> 1
+// All activations live in LDS; the packed weights (about 72 KB at k=24, L=6)
+// are read from global memory / L2, every workgroup reads the same ones.
+// fp32 operands, fp32 FMA accumulation. Every output element is produced by
+// exactly one thread looping (tap, ci) in a fixed order, so a position's
+// logits and table do not depend on what else is in the launch: the encoder
+// (one launch over all positions) and the decoder (one launch per wave)
+// produce bit-identical tables by construction.
+//
+// Masks are structural. In the flattened (d, kh, kw) order of the 2x3x3
+// filter the live taps are exactly the first 13 (first_mask) or 14
+// (other_mask) indices; only those are packed and only those are read.
+//
+// Packed weight layout (fp32, kp = k rounded up to a multiple of 8, padded
+// output channels hold zeros and are never read as inputs):
+//   w0[13][1][kp] b0[kp] w1[14][k][kp] b1[kp] w2[14][k][kp] b2[kp]
+//   w3[14][k][L]  b3[L]
+//
+// Tables: stabilised fp32 softmax, f = max(1, floor(p * (65536 - L))), so
+// tot <= 65535 and the coder's range / tot is never 0.
+
+#include "common.h"
+#include "rc_coder.h"
+
+namespace dsin {
+
+constexpr int PC_MAX_K = 32;
+constexpr int PC_MAX_L = rc::MAX_L;
+constexpr int PC_THREADS = 256;
+constexpr int PC_NT_FIRST = 13;
+constexpr int PC_NT_OTHER = 14;
+constexpr int PC_S0 = 4 * 7 * 7;   // conv0 output sites
+constexpr int PC_S1 = 3 * 5 * 5;   // res_conv1 output sites
+constexpr int PC_S2 = 2 * 3 * 3;   // res_conv2 output sites
+constexpr int PC_SIN = 5 * 9 * 9;  // context sites
+
+template <int CG> struct WVec;
+template <> struct WVec<8> {
+  float v[8];
+  __device__ __forceinline__ void load(const float* p) {
+    float4 a = *reinterpret_cast<const float4*>(p);
+    float4 b = *reinterpret_cast<const float4*>(p + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+  }
+};
+template <> struct WVec<2> {
+  float v[2];
+  __device__ __forceinline__ void load(const float* p) {
+    float2 a = *reinterpret_cast<const float2*>(p);
+    v[0] = a.x; v[1] = a.y;
+  }
+};
+
+// One masked VALID conv layer on LDS activations. in: [cin][Di*Hi*Wi],
+// out: [kp][Do*Ho*Wo]. A work item is (group of CG output channels, output
+// site); sites are the fast index so a wave reads consecutive LDS words.
+template <int CG, int NT, int Di, int Hi, int Wi, bool RELU, bool SKIP>
+__device__ __forceinline__ void pc_layer(const float* in, float* out,
+                                         const float* __restrict__ w,
+                                         const float* __restrict__ b, int cin,
+                                         int kp, const float* skip) {
+  constexpr int Ho = Hi - 2, Wo = Wi - 2;
+  constexpr int Si = Di * Hi * Wi, So = (Di - 1) * Ho * Wo;
+  const int items = So * (kp / CG);
+  for (int item = threadIdx.x; item < items; item += PC_THREADS) {
+    const int g = item / So, p = item - g * So;
+    const int d = p / (Ho * Wo), rem = p - d * (Ho * Wo);
+    const int h = rem / Wo, x = rem - h * Wo;
+    const int base = d * Hi * Wi + h * Wi + x;
+    const int co0 = g * CG;
+    float acc[CG];
+#pragma unroll
+    for (int j = 0; j < CG; ++j) acc[j] = b[co0 + j];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int off = (t / 9) * Hi * Wi + ((t % 9) / 3) * Wi + (t % 3);
+      const float* wt = w + (size_t)t * cin * kp + co0;
+      const float* it = in + base + off;
+#pragma unroll 4
+      for (int ci = 0; ci < cin; ++ci) {
+        const float v = it[ci * Si];
+        WVec<CG> wv;
+        wv.load(wt + ci * kp);
+#pragma unroll
+        for (int j = 0; j < CG; ++j) acc[j] = fmaf(v, wv.v[j], acc[j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < CG; ++j) {
+      float r = acc[j];
+      if (SKIP)
+        r += skip[(co0 + j) * PC_S0 + (d + 2) * 49 + (h + 2) * 7 + (x + 2)];
+      if (RELU) r = fmaxf(r, 0.f);
+      out[(co0 + j) * So + p] = r;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(PC_THREADS)
+pc_freqs_kernel(const float* __restrict__ q_pad, int C, int H, int W,
+                const int* __restrict__ pos, const float* __restrict__ wts,
+                int k, int kp, int L, float* __restrict__ logits,
+                int* __restrict__ freqs) {
+  __shared__ float s_in[PC_SIN + 3];
+  __shared__ float s_a0[PC_MAX_K * PC_S0];
+  __shared__ float s_a1[PC_MAX_K * PC_S1];
+  __shared__ float s_a2[PC_MAX_K * PC_S2];
+  __shared__ float s_part[PC_NT_OTHER * PC_MAX_L];
+  __shared__ float s_lg[PC_MAX_L];
+
+  const int64_t b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int c = pos[3 * b], h = pos[3 * b + 1], w = pos[3 * b + 2];
+  if (c < 0 || c >= C || h < 0 || h >= H || w < 0 || w >= W) {
+    if (tid < L) {  // never reached through the Python wrappers
+      logits[b * L + tid] = 0.f;
+      freqs[b * L + tid] = 1;
+    }
+    return;
+  }
+  const int Hp = H + 8, Wp = W + 8;
+  for (int i = tid; i < PC_SIN; i += PC_THREADS) {
+    const int d = i / 81, r = i - d * 81, y = r / 9, x = r - y * 9;
+    s_in[i] = q_pad[((int64_t)(c + d) * Hp + (h + y)) * Wp + (w + x)];
+  }
+  const float* w0 = wts;
+  const float* b0 = w0 + PC_NT_FIRST * kp;
+  const float* w1 = b0 + kp;
+  const float* b1 = w1 + (size_t)PC_NT_OTHER * k * kp;
+  const float* w2 = b1 + kp;
+  const float* b2 = w2 + (size_t)PC_NT_OTHER * k * kp;
+  const float* w3 = b2 + kp;
+  const float* b3 = w3 + (size_t)PC_NT_OTHER * k * L;
+  __syncthreads();
+  pc_layer<8, PC_NT_FIRST, 5, 9, 9, true, false>(s_in, s_a0, w0, b0, 1, kp,
+                                                 nullptr);
+  __syncthreads();
+  pc_layer<8, PC_NT_OTHER, 4, 7, 7, true, false>(s_a0, s_a1, w1, b1, k, kp,
+                                                 nullptr);
+  __syncthreads();
+  pc_layer<2, PC_NT_OTHER, 3, 5, 5, false, true>(s_a1, s_a2, w2, b2, k, kp,
+                                                 s_a0);
+  __syncthreads();
+  // conv2: one output site; tap t of the 2x3x3 input is site t. Thread
+  // (t, l) sums over ci, then thread l adds the 14 partials in tap order.
+  if (tid < PC_NT_OTHER * L) {
+    const int t = tid / L, l = tid - t * L;
+    float acc = 0.f;
+    const float* wt = w3 + (size_t)t * k * L + l;
+    for (int ci = 0; ci < k; ++ci)
+      acc = fmaf(s_a2[ci * PC_S2 + t], wt[ci * L], acc);
+    s_part[t * PC_MAX_L + l] = acc;
+  }
+  __syncthreads();
+  if (tid < L) {
+    float acc = b3[tid];
+    for (int t = 0; t < PC_NT_OTHER; ++t) acc += s_part[t * PC_MAX_L + tid];
+    s_lg[tid] = acc;
+  }
+  __syncthreads();
+  if (tid < L) {
+    float m = s_lg[0];
+    for (int l = 1; l < L; ++l) m = fmaxf(m, s_lg[l]);
+    float sum = 0.f;
+    for (int l = 0; l < L; ++l) sum += expf(s_lg[l] - m);
+    const float p = expf(s_lg[tid] - m) / sum;
+    int f = (int)floorf(p * (float)(65536 - L));
+    logits[b * L + tid] = s_lg[tid];
+    freqs[b * L + tid] = f < 1 ? 1 : f;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Range coder kernels. One lane runs the coder; the other lanes of the
+// workgroup only stage its operands in LDS (per-symbol cum/freq/tot for the
+// encoder; cumulative table rows and a window of the byte stream for the
+// decoder) and scatter the decoded symbols.
+// ---------------------------------------------------------------------------
+
+constexpr int RC_CHUNK = 256;
+constexpr int RC_WIN = RC_CHUNK * rc::MAX_SHIFTS;  // bytes a chunk can read
+
+// out: 8 bytes little-endian payload length, then the payload (cap bytes).
+__global__ void __launch_bounds__(RC_CHUNK)
+rc_encode_kernel(const int* __restrict__ syms, const int* __restrict__ freqs,
+                 int64_t n, int L, uint8_t* __restrict__ out, uint64_t cap) {
+  __shared__ uint32_t s_cum[RC_CHUNK], s_f[RC_CHUNK], s_tot[RC_CHUNK];
+  const int tid = threadIdx.x;
+  rc::State st;
+  rc::init(st);
+  const rc::ByteSink sink{out + 8, cap};
+  for (int64_t base = 0; base < n; base += RC_CHUNK) {
+    const int64_t i = base + tid;
+    if (i < n) {
+      int s = syms[i];
+      s = s < 0 ? 0 : (s >= L ? L - 1 : s);
+      const int* f = freqs + i * L;
+      uint32_t cum = 0, tot = 0, fs = 0;
+      for (int l = 0; l < L; ++l) {
+        const uint32_t v = (uint32_t)f[l];
+        if (l < s) cum += v;
+        if (l == s) fs = v;
+        tot += v;
+      }
+      s_cum[tid] = cum; s_f[tid] = fs; s_tot[tid] = tot;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      const int m = (int)((n - base) < RC_CHUNK ? (n - base) : RC_CHUNK);
+      for (int j = 0; j < m; ++j)
+        rc::encode(st, sink, s_cum[j], s_f[j], s_tot[j]);
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    rc::finish(st, sink);
+    for (int i = 0; i < 8; ++i) out[i] = (uint8_t)((st.pos >> (8 * i)) & 0xFF);
+  }
+}
+
+__global__ void rc_decode_init_kernel(rc::State* state,
+                                      const uint8_t* __restrict__ data,
+                                      uint64_t len) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    rc::State st;
+    rc::decode_start(st, rc::ByteSource{data, len});
+    *state = st;
+  }
+}
+
+struct WindowSource {
+  const uint8_t* win;   // LDS copy of data[base, base + RC_WIN), zero filled
+  uint64_t base;
+  const uint8_t* data;
+  uint64_t len;
+  __device__ __forceinline__ uint8_t get(uint64_t pos) const {
+    if (pos >= len) return 0;
+    if (pos >= base && pos - base < (uint64_t)RC_WIN) return win[pos - base];
+    return data[pos];
+  }
+};
+
+// Decodes nw symbols against freqs (nw, L), advancing *state. With pos set,
+// symbol i goes to out[c, h, w] and centers[s] into q_pad at that position;
+// with pos == nullptr it goes to out[i].
+__global__ void __launch_bounds__(RC_CHUNK)
+rc_decode_wave_kernel(rc::State* state, const uint8_t* __restrict__ data,
+                      uint64_t len, const int* __restrict__ freqs,
+                      const int* __restrict__ pos, int64_t nw, int L,
+                      const float* __restrict__ centers,
+                      float* __restrict__ q_pad, int C, int H, int W,
+                      int64_t* __restrict__ out) {
+  __shared__ uint32_t s_cum[RC_CHUNK * (rc::MAX_L + 1)];
+  __shared__ uint8_t s_win[RC_WIN];
+  __shared__ int s_sym[RC_CHUNK];
+  __shared__ rc::State s_state;
+  const int tid = threadIdx.x;
+  if (tid == 0) s_state = *state;
+  __syncthreads();
+  for (int64_t base = 0; base < nw; base += RC_CHUNK) {
+    const int m = (int)((nw - base) < RC_CHUNK ? (nw - base) : RC_CHUNK);
+    const uint64_t wbase = s_state.pos;
+    for (int i = tid; i < RC_WIN; i += RC_CHUNK)
+      s_win[i] = (wbase + i < len) ? data[wbase + i] : (uint8_t)0;
+    if (tid < m)  // every lane builds the cumulative row of its symbol
+      rc::cumulate(freqs + (base + tid) * L, L, s_cum + tid * (rc::MAX_L + 1));
+    __syncthreads();
+    if (tid == 0) {
+      rc::State st = s_state;
+      const WindowSource src{s_win, wbase, data, len};
+      for (int j = 0; j < m; ++j)
+        s_sym[j] = rc::decode_cum(st, src, s_cum + j * (rc::MAX_L + 1), L);
+      s_state = st;
+    }
+    __syncthreads();
+    if (tid < m) {
+      const int s = s_sym[tid];
+      const int64_t i = base + tid;
+      if (pos == nullptr) {
+        out[i] = s;
+      } else {
+        const int c = pos[3 * i], h = pos[3 * i + 1], w = pos[3 * i + 2];
+        if (c >= 0 && c < C && h >= 0 && h < H && w >= 0 && w < W) {
+          out[((int64_t)c * H + h) * W + w] = s;
+          q_pad[((int64_t)(c + 4) * (H + 8) + (h + 4)) * (W + 8) + (w + 4)] =
+              centers[s];
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) *state = s_state;
+}
+
+// ---------------------------------------------------------------------------
+// Host wrappers
+// ---------------------------------------------------------------------------
+
+static int64_t pc_packed_numel(int64_t k, int64_t L) {
+  const int64_t kp = (k + 7) / 8 * 8;
+  return PC_NT_FIRST * kp + kp + 2 * (PC_NT_OTHER * k * kp + kp) +
+         PC_NT_OTHER * k * L + L;
+}
+
+static void pc_check(const torch::Tensor& q_pad, const torch::Tensor& pos,
+                     const torch::Tensor& wts, int64_t k, int64_t L) {
+  CHECK_CUDA_CONTIG(q_pad);
+  CHECK_CUDA_CONTIG(pos);
+  CHECK_CUDA_CONTIG(wts);
+  TORCH_CHECK(k >= 1 && k <= PC_MAX_K, "pc_codec: k must be in [1, ",
+              PC_MAX_K, "]");
+  TORCH_CHECK(L >= 1 && L <= PC_MAX_L, "pc_codec: L must be in [1, ",
+              PC_MAX_L, "]");
+  TORCH_CHECK(q_pad.scalar_type() == torch::kFloat32 && q_pad.dim() == 3 &&
+                  q_pad.size(0) > 4 && q_pad.size(1) > 8 && q_pad.size(2) > 8,
+              "pc_codec: q_pad must be fp32 (C+4, H+8, W+8)");
+  TORCH_CHECK(pos.scalar_type() == torch::kInt32 && pos.dim() == 2 &&
+                  pos.size(1) == 3,
+              "pc_codec: positions must be int32 (n, 3)");
+  TORCH_CHECK(wts.scalar_type() == torch::kFloat32 &&
+                  wts.numel() == pc_packed_numel(k, L),
+              "pc_codec: packed weights have the wrong size");
+}
+
+static void launch_pc_freqs(const torch::Tensor& q_pad, const int* pos,
+                            int64_t n, const torch::Tensor& wts, int64_t k,
+                            int64_t L, float* logits, int* freqs) {
+  if (n == 0) return;
+  const int C = (int)q_pad.size(0) - 4, H = (int)q_pad.size(1) - 8,
+            W = (int)q_pad.size(2) - 8;
+  const int kp = (int)((k + 7) / 8 * 8);
+  hipLaunchKernelGGL(pc_freqs_kernel, dim3((unsigned)n), dim3(PC_THREADS), 0,
+                     at::cuda::getCurrentCUDAStream(),
+                     q_pad.data_ptr<float>(), C, H, W, pos,
+                     wts.data_ptr<float>(), (int)k, kp, (int)L, logits, freqs);
+}
+
+std::tuple<torch::Tensor, torch::Tensor> pc_freqs(torch::Tensor q_pad,
+                                                  torch::Tensor pos,
+                                                  torch::Tensor wts, int64_t k,
+                                                  int64_t L) {
+  pc_check(q_pad, pos, wts, k, L);
+  const int64_t n = pos.size(0);
+  auto logits = torch::empty({n, L}, q_pad.options());
+  auto freqs = torch::empty({n, L}, pos.options());
+  launch_pc_freqs(q_pad, pos.data_ptr<int>(), n, wts, k, L,
+                  logits.data_ptr<float>(), freqs.data_ptr<int>());
+  return {logits, freqs};
+}
+
+// (8 + 3n + 16) bytes: little-endian payload length, then the payload.
+torch::Tensor rc_encode(torch::Tensor syms, torch::Tensor freqs) {
+  CHECK_CUDA_CONTIG(syms);
+  CHECK_CUDA_CONTIG(freqs);
+  TORCH_CHECK(syms.scalar_type() == torch::kInt32 && syms.dim() == 1,
+              "rc_encode: symbols must be int32 (n,)");
+  TORCH_CHECK(freqs.scalar_type() == torch::kInt32 && freqs.dim() == 2 &&
+                  freqs.size(0) == syms.size(0) && freqs.size(1) >= 1 &&
+                  freqs.size(1) <= PC_MAX_L,
+              "rc_encode: tables must be int32 (n, L<=16)");
+  const int64_t n = syms.size(0), L = freqs.size(1);
+  const int64_t cap = 3 * n + 16;
+  auto out = torch::empty({8 + cap}, syms.options().dtype(torch::kUInt8));
+  hipLaunchKernelGGL(rc_encode_kernel, dim3(1), dim3(RC_CHUNK), 0,
+                     at::cuda::getCurrentCUDAStream(), syms.data_ptr<int>(),
+                     freqs.data_ptr<int>(), n, (int)L,
+                     out.data_ptr<uint8_t>(), (uint64_t)cap);
+  return out;
+}
+
+torch::Tensor pc_encode(torch::Tensor q_pad, torch::Tensor pos,
+                        torch::Tensor syms, torch::Tensor wts, int64_t k,
+                        int64_t L) {
+  TORCH_CHECK(syms.dim() == 1 && syms.size(0) == pos.size(0),
+              "pc_encode: one symbol per position");
+  auto lf = pc_freqs(q_pad, pos, wts, k, L);
+  return rc_encode(syms, std::get<1>(lf));
+}
+
+static torch::Tensor decode_state(const torch::Tensor& data) {
+  auto state = torch::empty({(int64_t)(sizeof(rc::State) / 8)},
+                            data.options().dtype(torch::kInt64));
+  hipLaunchKernelGGL(rc_decode_init_kernel, dim3(1), dim3(1), 0,
+                     at::cuda::getCurrentCUDAStream(),
+                     reinterpret_cast<rc::State*>(state.data_ptr<int64_t>()),
+                     data.data_ptr<uint8_t>(), (uint64_t)data.numel());
+  return state;
+}
+
+// Decode n symbols against given tables (n, L) in one launch.
+torch::Tensor rc_decode(torch::Tensor data, torch::Tensor freqs) {
+  CHECK_CUDA_CONTIG(data);
+  CHECK_CUDA_CONTIG(freqs);
+  TORCH_CHECK(data.scalar_type() == torch::kUInt8 && data.dim() == 1,
+              "rc_decode: data must be uint8 (len,)");
+  TORCH_CHECK(freqs.scalar_type() == torch::kInt32 && freqs.dim() == 2 &&
+                  freqs.size(1) >= 1 && freqs.size(1) <= PC_MAX_L,
+              "rc_decode: tables must be int32 (n, L<=16)");
+  const int64_t n = freqs.size(0), L = freqs.size(1);
+  auto out = torch::zeros({n}, freqs.options().dtype(torch::kInt64));
+  if (n == 0) return out;
+  auto state = decode_state(data);
+  hipLaunchKernelGGL(rc_decode_wave_kernel, dim3(1), dim3(RC_CHUNK), 0,
+                     at::cuda::getCurrentCUDAStream(),
+                     reinterpret_cast<rc::State*>(state.data_ptr<int64_t>()),
+                     data.data_ptr<uint8_t>(), (uint64_t)data.numel(),
+                     freqs.data_ptr<int>(), (const int*)nullptr, n, (int)L,
+                     (const float*)nullptr, (float*)nullptr, 0, 0, 0,
+                     out.data_ptr<int64_t>());
+  return out;
+}
+
+// Wavefront decode: wave i covers pos[offsets[i], offsets[i+1]). Two
+// launches per wave on the current stream, no host synchronisation. q_pad is
+// filled in place; returns the (C, H, W) int64 symbols.
+torch::Tensor pc_decode(torch::Tensor q_pad, torch::Tensor pos,
+                        std::vector<int64_t> offsets, torch::Tensor wts,
+                        int64_t k, int64_t L, torch::Tensor data,
+                        torch::Tensor centers) {
+  pc_check(q_pad, pos, wts, k, L);
+  CHECK_CUDA_CONTIG(data);
+  CHECK_CUDA_CONTIG(centers);
+  TORCH_CHECK(data.scalar_type() == torch::kUInt8 && data.dim() == 1,
+              "pc_decode: data must be uint8 (len,)");
+  TORCH_CHECK(centers.scalar_type() == torch::kFloat32 &&
+                  centers.numel() == L,
+              "pc_decode: centers must be fp32 (L,)");
+  const int64_t n = pos.size(0);
+  TORCH_CHECK(offsets.size() >= 1 && offsets.front() == 0 &&
+                  offsets.back() == n,
+              "pc_decode: wave offsets must run from 0 to n");
+  int64_t maxw = 0;
+  for (size_t i = 1; i < offsets.size(); ++i) {
+    TORCH_CHECK(offsets[i] >= offsets[i - 1],
+                "pc_decode: wave offsets must not decrease");
+    maxw = std::max(maxw, offsets[i] - offsets[i - 1]);
+  }
+  const int C = (int)q_pad.size(0) - 4, H = (int)q_pad.size(1) - 8,
+            W = (int)q_pad.size(2) - 8;
+  auto out = torch::zeros({C, H, W}, pos.options().dtype(torch::kInt64));
+  if (n == 0) return out;
+  auto logits = torch::empty({maxw, L}, q_pad.options());
+  auto freqs = torch::empty({maxw, L}, pos.options());
+  auto state = decode_state(data);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const int* p = pos.data_ptr<int>();
+  for (size_t i = 1; i < offsets.size(); ++i) {
+    const int64_t o = offsets[i - 1], nw = offsets[i] - o;
+    if (nw == 0) continue;
+    launch_pc_freqs(q_pad, p + 3 * o, nw, wts, k, L, logits.data_ptr<float>(),
+                    freqs.data_ptr<int>());
+    hipLaunchKernelGGL(rc_decode_wave_kernel, dim3(1), dim3(RC_CHUNK), 0,
+                       stream,
+                       reinterpret_cast<rc::State*>(state.data_ptr<int64_t>()),
+                       data.data_ptr<uint8_t>(), (uint64_t)data.numel(),
+                       freqs.data_ptr<int>(), p + 3 * o, nw, (int)L,
+                       centers.data_ptr<float>(), q_pad.data_ptr<float>(), C,
+                       H, W, out.data_ptr<int64_t>());
+  }
+  return out;
+}
+
+// Host build of the same step functions (CPU tensors), for the tests.
+torch::Tensor rc_encode_host(torch::Tensor syms, torch::Tensor freqs) {
+  TORCH_CHECK(!syms.is_cuda() && !freqs.is_cuda() && syms.is_contiguous() &&
+                  freqs.is_contiguous(),
+              "rc_encode_host: CPU contiguous tensors");
+  TORCH_CHECK(syms.scalar_type() == torch::kInt32 && syms.dim() == 1 &&
+                  freqs.scalar_type() == torch::kInt32 && freqs.dim() == 2 &&
+                  freqs.size(0) == syms.size(0) && freqs.size(1) >= 1 &&
+                  freqs.size(1) <= PC_MAX_L,
+              "rc_encode_host: int32 (n,) symbols and (n, L<=16) tables");
+  const int64_t n = syms.size(0), L = freqs.size(1);
+  const int64_t cap = 3 * n + 16;
+  auto out = torch::zeros({cap}, torch::kUInt8);
+  rc::State st;
+  rc::init(st);
+  const rc::ByteSink sink{out.data_ptr<uint8_t>(), (uint64_t)cap};
+  const int* sp = syms.data_ptr<int>();
+  const int* fp = freqs.data_ptr<int>();
+  for (int64_t i = 0; i < n; ++i) {
+    int s = sp[i] < 0 ? 0 : (sp[i] >= L ? (int)L - 1 : sp[i]);
+    uint32_t cum = 0, tot = 0;
+    for (int l = 0; l < L; ++l) {
+      if (l < s) cum += (uint32_t)fp[i * L + l];
+      tot += (uint32_t)fp[i * L + l];
+    }
+    rc::encode(st, sink, cum, (uint32_t)fp[i * L + s], tot);
+  }
+  rc::finish(st, sink);
+  TORCH_CHECK((int64_t)st.pos <= cap, "rc_encode_host: stream overran ", cap,
+              " bytes");
+  return out.slice(0, 0, (int64_t)st.pos).clone();
+}
+
+torch::Tensor rc_decode_host(torch::Tensor data, torch::Tensor freqs) {
+  TORCH_CHECK(!data.is_cuda() && !freqs.is_cuda() && data.is_contiguous() &&
+                  freqs.is_contiguous(),
+              "rc_decode_host: CPU contiguous tensors");
+  TORCH_CHECK(data.scalar_type() == torch::kUInt8 && data.dim() == 1 &&
+                  freqs.scalar_type() == torch::kInt32 && freqs.dim() == 2 &&
+                  freqs.size(1) >= 1 && freqs.size(1) <= PC_MAX_L,
+              "rc_decode_host: uint8 data and int32 (n, L<=16) tables");
+  const int64_t n = freqs.size(0), L = freqs.size(1);
+  auto out = torch::zeros({n}, torch::kInt32);
+  const rc::ByteSource src{data.data_ptr<uint8_t>(), (uint64_t)data.numel()};
+  rc::State st;
+  rc::decode_start(st, src);
+  const int* fp = freqs.data_ptr<int>();
+  int* op = out.data_ptr<int>();
+  uint32_t cum[rc::MAX_L + 1];
+  for (int64_t i = 0; i < n; ++i) {
+    rc::cumulate(fp + i * L, (int)L, cum);
+    op[i] = rc::decode_cum(st, src, cum, (int)L);
+  }
+  return out;
+}
+
+}  // namespace dsin

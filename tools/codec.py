@@ -1,0 +1,128 @@
+"""Compress a PNG to a .dsin byte stream and back.
+
+    python tools/codec.py compress   <checkpoint> <x.png> <out.dsin>
+    python tools/codec.py decompress <checkpoint> <in.dsin> [--side y.png] <out.png>
+
+<checkpoint> is a directory written by training (it holds model.pt). The
+model runs on the GPU when there is one (hip codec backend) and on the CPU
+otherwise (torch backend); a stream is decoded by the backend that wrote
+it (see dsin_amd/coding/bitstream.py). With --side the decoder also runs
+the side-information search and fusion and writes x_with_si; without it,
+x_dec. Image height and width must be multiples of 8, and with --side they
+must tile by the patch size (--patch HxW, default from the config or the
+largest of 20/16/8.. x 24/32/16.. that divides the image).
+"""
+
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np
+import torch
+
+from dsin_amd import config as config_mod
+from dsin_amd.coding import compress, decompress
+from dsin_amd.coding.bitstream import parse_container
+from dsin_amd.data.png import read_png, write_png
+from dsin_amd.models import DSIN
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def load_image(path: str, device) -> torch.Tensor:
+    img = read_png(path)
+    if img.shape[2] == 1:
+        img = np.repeat(img, 3, axis=2)
+    img = img[:, :, :3]
+    if img.shape[0] % 8 or img.shape[1] % 8:
+        sys.exit(f"{path}: {img.shape[0]}x{img.shape[1]} is not a multiple "
+                 f"of 8 in both dimensions")
+    return torch.from_numpy(img.copy()).permute(2, 0, 1).float().to(device)
+
+
+def save_image(path: str, x: torch.Tensor) -> None:
+    img = x.detach().float().clamp(0, 255).round().to(torch.uint8)
+    write_png(path, img[0].permute(1, 2, 0).cpu().numpy())
+
+
+def build_model(args, height: int, width: int, device) -> DSIN:
+    ae, _ = config_mod.parse(args.ae_config)
+    pc, _ = config_mod.parse(args.pc_config)
+    ae.crop_size = (height, width)
+    if args.patch:
+        ph, pw = (int(v) for v in args.patch.split("x"))
+    else:
+        ph, pw = ae.y_patch_size
+        if height % ph or width % pw:
+            ph = next(p for p in (20, 16, 32, 8, 4, 2, 1) if height % p == 0)
+            pw = next(p for p in (24, 32, 16, 8, 4, 2, 1) if width % p == 0)
+    ae.y_patch_size = (ph, pw)
+    model = DSIN(ae, pc)
+    blob = torch.load(os.path.join(args.checkpoint, "model.pt"),
+                      map_location="cpu", weights_only=False)
+    for name, mod in model.state_groups().items():
+        if name not in blob:
+            sys.exit(f"{args.checkpoint}: checkpoint has no {name!r} group")
+        mod.load_state_dict(blob[name])
+    return model.to(device).eval()
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--ae-config", default=os.path.join(
+        ROOT, "run_configs", "ae_run_configs"))
+    ap.add_argument("--pc-config", default=os.path.join(
+        ROOT, "run_configs", "pc_run_configs"))
+    ap.add_argument("--device", default=None)
+    ap.add_argument("--bf16", action="store_true",
+                    help="bf16 autocast for the autoencoder (GPU); use the "
+                         "same setting on both sides")
+    ap.add_argument("--patch", default=None, help="side-info patch size HxW")
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    c = sub.add_parser("compress")
+    c.add_argument("checkpoint")
+    c.add_argument("image")
+    c.add_argument("out")
+    d = sub.add_parser("decompress")
+    d.add_argument("checkpoint")
+    d.add_argument("stream")
+    d.add_argument("--side", default=None, help="side image y.png")
+    d.add_argument("out")
+    args = ap.parse_args()
+
+    device = torch.device(args.device or (
+        "cuda:0" if torch.cuda.is_available() else "cpu"))
+    cast = torch.autocast("cuda", dtype=torch.bfloat16, cache_enabled=False,
+                          enabled=args.bf16 and device.type == "cuda")
+    if args.cmd == "compress":
+        x = load_image(args.image, device)
+        model = build_model(args, x.shape[1], x.shape[2], device)
+        with cast:
+            data = compress(model, x)
+        with open(args.out, "wb") as f:
+            f.write(data)
+        bpp = 8.0 * len(data) / (x.shape[1] * x.shape[2])
+        print(f"{args.out}: {len(data)} bytes, {bpp:.4f} bpp")
+    else:
+        with open(args.stream, "rb") as f:
+            data = f.read()
+        try:
+            _, (_, hb, wb), _, _, _ = parse_container(data)
+        except ValueError as e:
+            sys.exit(f"{args.stream}: {e}")
+        model = build_model(args, hb * 8, wb * 8, device)
+        y = load_image(args.side, device) if args.side else None
+        try:
+            with cast:
+                x_dec, x_si = decompress(model, data, y)
+        except ValueError as e:
+            sys.exit(f"{args.stream}: {e}")
+        save_image(args.out, x_si if x_si is not None else x_dec)
+        print(f"{args.out}: {hb * 8}x{wb * 8}, "
+              f"{'x_with_si' if x_si is not None else 'x_dec'}")
+
+
+if __name__ == "__main__":
+    main()
