@@ -7,6 +7,8 @@ fixed-normalized, H1H2H3-decorrelated values, weighted by a Gaussian location
 prior), then gather the winning patches FROM THE ORIGINAL y and scatter them
 back into an image. Mirror of /root/reference/src/siFull_img.py:5-68 +
 src/siFinder.py:7-135 + the mask construction at src/AE.py:193-220.
+With use_L2andLAB the score is the squared L2 distance of CIELAB values and
+the winner its minimum (same op, l2lab=True; same kernels on the GPU).
 
 The whole search is non-trainable (reference src/siFinder.py:3-5) and y_syn
 is consumed under stop_gradient (src/AE.py:67), so this path runs without
@@ -27,12 +29,6 @@ class SiFinder(torch.nn.Module):
         self.ph, self.pw = (int(v) for v in config.y_patch_size)
         self.use_mask = bool(config.use_gauss_mask)
         self.l2lab = bool(config.use_L2andLAB)
-        if self.l2lab:
-            import warnings
-            warnings.warn(
-                "use_L2andLAB runs on the torch path (correct but slower "
-                "than the streaming HIP NCC kernel used for the shipped "
-                "Pearson+H1H2H3 mode)")
 
     @torch.no_grad()
     def forward(self, x_dec: torch.Tensor, y_orig: torch.Tensor,

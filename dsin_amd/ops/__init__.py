@@ -247,18 +247,28 @@ def ncc_search(x_dec: torch.Tensor, y_dec: torch.Tensor, y_orig: torch.Tensor,
                ph: int, pw: int, use_mask: bool = True, l2lab: bool = False
                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Single-image SI search: (3,Hx,Wx)x3 -> (y_syn (3,Hx,Wx), rows, cols).
-    l2lab selects the reference's use_L2andLAB mode (LAB transform +
-    argmin of squared L2) — served by the torch path on every device; the
-    streaming HIP kernel covers the Pearson+H1H2H3 mode of the shipped
-    configs."""
+    l2lab selects the reference's use_L2andLAB mode: CIELAB of the raw
+    images, squared L2 distance (times the prior when use_mask), argmin
+    with the first index on ties. On the GPU both modes run the streaming
+    HIP kernels (bf16 operands, fp32 scores, no (P,Hc,Wc) volume, no host
+    sync); on the CPU both run the torch reference in fp32."""
     check_ncc_inputs(x_dec, y_dec, y_orig, ph, pw, use_mask)
-    if x_dec.is_cuda and not l2lab:
-        fn = _require_ext("ncc_search")
+    if x_dec.is_cuda:
+        fn = _require_ext("ncc_search_l2lab" if l2lab else "ncc_search")
         y_syn, rows, cols = fn(x_dec.contiguous().float(), y_dec.contiguous().float(),
                                y_orig.contiguous().float(), ph, pw, use_mask)
         return y_syn, rows, cols
     return ref.ncc_search_ref(x_dec.float(), y_dec.float(), y_orig.float(),
                               ph, pw, use_mask, l2lab=l2lab)
+
+
+@torch.no_grad()
+def ncc_lab_transform(img: torch.Tensor) -> torch.Tensor:
+    """(3,H,W) raw pixels -> the bf16 CIELAB operands of the l2lab search.
+    GPU: the kernel the search itself runs; CPU: rgb_to_lab_ref rounded."""
+    if img.is_cuda:
+        return _require_ext("ncc_lab_transform")(img.contiguous().float())
+    return ref.rgb_to_lab_ref(img.float()).to(torch.bfloat16)
 
 
 # ---------------------------------------------------------------------------

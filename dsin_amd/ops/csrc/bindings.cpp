@@ -15,6 +15,10 @@ torch::Tensor bitcost_ce_bwd(torch::Tensor g, torch::Tensor logits,
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search(
     torch::Tensor x_dec, torch::Tensor y_dec, torch::Tensor y_orig, int64_t ph,
     int64_t pw, bool use_mask);
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search_l2lab(
+    torch::Tensor x_dec, torch::Tensor y_dec, torch::Tensor y_orig, int64_t ph,
+    int64_t pw, bool use_mask);
+torch::Tensor ncc_lab_transform(torch::Tensor img);
 torch::Tensor mfma_selftest(torch::Tensor A, torch::Tensor B);
 torch::Tensor mfma32_selftest(torch::Tensor A, torch::Tensor B);
 std::tuple<torch::Tensor, torch::Tensor> conv_tables(
@@ -93,6 +97,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bitcost_ce_fwd", &dsin::bitcost_ce_fwd, "bitcost cross-entropy fwd");
   m.def("bitcost_ce_bwd", &dsin::bitcost_ce_bwd, "bitcost cross-entropy bwd");
   m.def("ncc_search", &dsin::ncc_search, "streaming NCC side-info search");
+  m.def("ncc_search_l2lab", &dsin::ncc_search_l2lab,
+        "streaming L2+LAB side-info search (argmin of squared distance)");
+  m.def("ncc_lab_transform", &dsin::ncc_lab_transform,
+        "bf16 CIELAB operands of the L2+LAB search");
   m.def("mfma_selftest", &dsin::mfma_selftest, "MFMA 16x16x32 layout check");
   m.def("mfma32_selftest", &dsin::mfma32_selftest, "MFMA 32x32x16 layout check");
   m.def("conv_tables", &dsin::conv_tables, "gather-conv offset tables");

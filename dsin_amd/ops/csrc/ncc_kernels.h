@@ -75,6 +75,42 @@ __global__ void transform_kernel(const float* __restrict__ img,
   }
 }
 
+// L2+LAB mode (use_L2andLAB): CIELAB of the RAW pixel values, as the
+// reference feeds them (0..255 straight into the sRGB gamma, no rescale, no
+// fixed-stats normalization). Both piecewise functions take their linear
+// branch at and below the threshold, which includes every negative value.
+__device__ __forceinline__ float lab_lin(float px) {
+  return px <= 0.04045f ? px / 12.92f
+                        : powf((px + 0.055f) / 1.055f, 2.4f);
+}
+
+__device__ __forceinline__ float lab_f(float t) {
+  constexpr float EPS3 = (float)((6.0 / 29.0) * (6.0 / 29.0) * (6.0 / 29.0));
+  constexpr float LIN = (float)(3.0 * (6.0 / 29.0) * (6.0 / 29.0));
+  return t <= EPS3 ? t / LIN + (float)(4.0 / 29.0) : cbrtf(t);
+}
+
+__global__ void lab_transform_kernel(const float* __restrict__ img,
+                                     ncbf16* __restrict__ out, long long hw) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  long long stride = (long long)gridDim.x * blockDim.x;
+  for (; i < hw; i += stride) {
+    const float r = lab_lin(img[i]);
+    const float g = lab_lin(img[hw + i]);
+    const float b = lab_lin(img[2 * hw + i]);
+    // linear RGB -> XYZ over the white point (0.950456, 1, 1.088754)
+    const float x = (0.412453f * r + 0.357580f * g + 0.180423f * b) *
+                    (float)(1.0 / 0.950456);
+    const float y = 0.212671f * r + 0.715160f * g + 0.072169f * b;
+    const float z = (0.019334f * r + 0.119193f * g + 0.950227f * b) *
+                    (float)(1.0 / 1.088754);
+    const float fx = lab_f(x), fy = lab_f(y), fz = lab_f(z);
+    out[i] = nf2b(116.f * fy - 16.f);
+    out[hw + i] = nf2b(500.f * (fx - fy));
+    out[2 * hw + i] = nf2b(200.f * (fy - fz));
+  }
+}
+
 // ---------------------------------------------------------------- stage 2
 
 __global__ void patch_stats_kernel(const ncbf16* __restrict__ tx,
@@ -146,7 +182,15 @@ __global__ void ysum_col_kernel(const float* __restrict__ s1,
 // Epilogue fully predicated (no divergent branches): fast rsqrt Pearson
 // normalization, inline Gaussian prior, packed (flipped-float | ~idx) u64
 // running max -> one atomicMax per patch at the end.
+//
+// L2 = true is the L2+LAB mode: same staging, MFMA loop and LDS layout; the
+// epilogue scores d = sum_x2 - 2*xy + sum_y2 (times the same prior) and the
+// winner is the MINIMUM, taken by the same atomicMax on the key of 0 - d
+// (the subtraction folds -0 into +0, so equal distances give one key and
+// the smallest index still wins). Pstat then holds sum_x2 in row 0 and the
+// two prior centres in rows 3 and 4; psum and sy are not read.
 
+template <bool L2>
 __global__ __launch_bounds__(256)
 void ncc_main_kernel(const ncbf16* __restrict__ tx, const ncbf16* __restrict__ ty,
                      const unsigned int* __restrict__ aoffs,
@@ -192,11 +236,15 @@ void ncc_main_kernel(const ncbf16* __restrict__ tx, const ncbf16* __restrict__ t
   for (int k = tid; k < KP; k += 256) Ko[k] = (k < K) ? koffs[k] : 0;
   if (tid < NCC_TP) {
     const int p = min(p0 + tid, P - 1);
-    const float sxv = psum[p];
-    const float xm = sxv * invK;
-    Pstat[tid] = sxv;
-    Pstat[NCC_TP + tid] = xm;
-    Pstat[2 * NCC_TP + tid] = psum2[p] - 2.f * xm * sxv + fK * xm * xm;
+    if constexpr (L2) {
+      Pstat[tid] = psum2[p];
+    } else {
+      const float sxv = psum[p];
+      const float xm = sxv * invK;
+      Pstat[tid] = sxv;
+      Pstat[NCC_TP + tid] = xm;
+      Pstat[2 * NCC_TP + tid] = psum2[p] - 2.f * xm * sxv + fK * xm * xm;
+    }
     Pstat[3 * NCC_TP + tid] = ((float)(p / gw) + 0.5f) * (float)ph;  // cr
     Pstat[4 * NCC_TP + tid] = ((float)(p % gw) + 0.5f) * (float)pw;  // cw
   }
@@ -272,31 +320,54 @@ void ncc_main_kernel(const ncbf16* __restrict__ tx, const ncbf16* __restrict__ t
       if (half == 1 && !i1ok) break;
       const int iw = ii + half;
       const long long sidx = (long long)iw * Wc + (jvalid ? j : 0);
-      const float syv = sy[sidx];
-      const float sy2v = sy2[sidx];
-      const float ym = syv * invK;
-      const float deny = sy2v - 2.f * ym * syv + fK * ym * ym;
       const float di = (float)(iw + ph / 2 - 1);
       const unsigned int idx = (unsigned int)(iw * Wc + j);
+      if constexpr (L2) {
+        const float sy2v = sy2[sidx];
 #pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int prow = (reg & 3) + 8 * (reg >> 2) + 4 * kgrp;
-        const float av = half == 0 ? acc0[reg] : acc1[reg];
-        const float sxv = Pstat[prow];
-        const float xm = Pstat[NCC_TP + prow];
-        const float denx = Pstat[2 * NCC_TP + prow];
-        const float num = av - ym * sxv - xm * syv + fK * xm * ym;
-        float val = num * __builtin_amdgcn_rsqf(fmaxf(denx * deny, NCC_EPS));
-        if (use_mask) {
-          const float dd = di - Pstat[3 * NCC_TP + prow];
-          const float dj = (float)(j + pw / 2 - 1) - Pstat[4 * NCC_TP + prow];
-          val *= __expf(-FOURLN2 * (dd * dd * ish2 + dj * dj * isw2));
+        for (int reg = 0; reg < 16; ++reg) {
+          const int prow = (reg & 3) + 8 * (reg >> 2) + 4 * kgrp;
+          const float av = half == 0 ? acc0[reg] : acc1[reg];
+          float val = Pstat[prow] - 2.f * av + sy2v;
+          if (use_mask) {
+            const float dd = di - Pstat[3 * NCC_TP + prow];
+            const float dj =
+                (float)(j + pw / 2 - 1) - Pstat[4 * NCC_TP + prow];
+            val *= __expf(-FOURLN2 * (dd * dd * ish2 + dj * dj * isw2));
+          }
+          unsigned long long key =
+              ((unsigned long long)nfloat_flip(0.f - val) << 32) |
+              (unsigned long long)(~idx);
+          key = (jvalid && (p0 + prow) < P) ? key : 0ull;
+          if (key > bestk[reg]) bestk[reg] = key;
         }
-        unsigned long long key =
-            ((unsigned long long)nfloat_flip(val) << 32) |
-            (unsigned long long)(~idx);
-        key = (jvalid && (p0 + prow) < P) ? key : 0ull;
-        if (key > bestk[reg]) bestk[reg] = key;
+      } else {
+        const float syv = sy[sidx];
+        const float sy2v = sy2[sidx];
+        const float ym = syv * invK;
+        const float deny = sy2v - 2.f * ym * syv + fK * ym * ym;
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+          const int prow = (reg & 3) + 8 * (reg >> 2) + 4 * kgrp;
+          const float av = half == 0 ? acc0[reg] : acc1[reg];
+          const float sxv = Pstat[prow];
+          const float xm = Pstat[NCC_TP + prow];
+          const float denx = Pstat[2 * NCC_TP + prow];
+          const float num = av - ym * sxv - xm * syv + fK * xm * ym;
+          float val =
+              num * __builtin_amdgcn_rsqf(fmaxf(denx * deny, NCC_EPS));
+          if (use_mask) {
+            const float dd = di - Pstat[3 * NCC_TP + prow];
+            const float dj =
+                (float)(j + pw / 2 - 1) - Pstat[4 * NCC_TP + prow];
+            val *= __expf(-FOURLN2 * (dd * dd * ish2 + dj * dj * isw2));
+          }
+          unsigned long long key =
+              ((unsigned long long)nfloat_flip(val) << 32) |
+              (unsigned long long)(~idx);
+          key = (jvalid && (p0 + prow) < P) ? key : 0ull;
+          if (key > bestk[reg]) bestk[reg] = key;
+        }
       }
     }
   }
@@ -335,6 +406,8 @@ constexpr int NCC_TJ2 = 64;  // v2 col tile: 2 j-waves x 32 — the y window
                              // L1 with two co-resident blocks; the other 2
                              // waves take the other 4-row output group
 
+// L2 = true: the L2+LAB epilogue and Pstat contents of ncc_main_kernel<true>
+template <bool L2>
 __global__ __launch_bounds__(256)
 void ncc_main_v2_kernel(const ncbf16* __restrict__ tx,
                         const ncbf16* __restrict__ ty,
@@ -368,11 +441,15 @@ void ncc_main_v2_kernel(const ncbf16* __restrict__ tx,
 
   if (tid < NCC_TP) {
     const int p = min(p0 + tid, P - 1);
-    const float sxv = psum[p];
-    const float xm = sxv * invK;
-    Pstat[tid] = sxv;
-    Pstat[NCC_TP + tid] = xm;
-    Pstat[2 * NCC_TP + tid] = psum2[p] - 2.f * xm * sxv + fK * xm * xm;
+    if constexpr (L2) {
+      Pstat[tid] = psum2[p];
+    } else {
+      const float sxv = psum[p];
+      const float xm = sxv * invK;
+      Pstat[tid] = sxv;
+      Pstat[NCC_TP + tid] = xm;
+      Pstat[2 * NCC_TP + tid] = psum2[p] - 2.f * xm * sxv + fK * xm * xm;
+    }
     Pstat[3 * NCC_TP + tid] = ((float)(p / gw) + 0.5f) * (float)ph;
     Pstat[4 * NCC_TP + tid] = ((float)(p % gw) + 0.5f) * (float)pw;
   }
@@ -421,30 +498,50 @@ void ncc_main_v2_kernel(const ncbf16* __restrict__ tx,
   // per-row epilogue (identical math to the v1 kernel)
   auto epilogue_row = [&](const f32x16& acc, int iw) {
     const long long sidx = (long long)iw * Wc + (jvalid ? j : 0);
-    const float syv = sy[sidx];
-    const float sy2v = sy2[sidx];
-    const float ym = syv * invK;
-    const float deny = sy2v - 2.f * ym * syv + fK * ym * ym;
     const float di = (float)(iw + ph / 2 - 1);
     const unsigned int idx = (unsigned int)(iw * Wc + j);
+    if constexpr (L2) {
+      const float sy2v = sy2[sidx];
 #pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-      const int prow = (reg & 3) + 8 * (reg >> 2) + 4 * kgrp;
-      const float av = acc[reg];
-      const float sxv = Pstat[prow];
-      const float xm = Pstat[NCC_TP + prow];
-      const float denx = Pstat[2 * NCC_TP + prow];
-      const float num = av - ym * sxv - xm * syv + fK * xm * ym;
-      float val = num * __builtin_amdgcn_rsqf(fmaxf(denx * deny, NCC_EPS));
-      if (use_mask) {
-        const float dd = di - Pstat[3 * NCC_TP + prow];
-        const float dj = (float)(j + pw / 2 - 1) - Pstat[4 * NCC_TP + prow];
-        val *= __expf(-FOURLN2 * (dd * dd * ish2 + dj * dj * isw2));
+      for (int reg = 0; reg < 16; ++reg) {
+        const int prow = (reg & 3) + 8 * (reg >> 2) + 4 * kgrp;
+        float val = Pstat[prow] - 2.f * acc[reg] + sy2v;
+        if (use_mask) {
+          const float dd = di - Pstat[3 * NCC_TP + prow];
+          const float dj = (float)(j + pw / 2 - 1) - Pstat[4 * NCC_TP + prow];
+          val *= __expf(-FOURLN2 * (dd * dd * ish2 + dj * dj * isw2));
+        }
+        unsigned long long key =
+            ((unsigned long long)nfloat_flip(0.f - val) << 32) |
+            (unsigned long long)(~idx);
+        key = (jvalid && (p0 + prow) < P) ? key : 0ull;
+        if (key > bestk[reg]) bestk[reg] = key;
       }
-      unsigned long long key = ((unsigned long long)nfloat_flip(val) << 32) |
-                               (unsigned long long)(~idx);
-      key = (jvalid && (p0 + prow) < P) ? key : 0ull;
-      if (key > bestk[reg]) bestk[reg] = key;
+    } else {
+      const float syv = sy[sidx];
+      const float sy2v = sy2[sidx];
+      const float ym = syv * invK;
+      const float deny = sy2v - 2.f * ym * syv + fK * ym * ym;
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) {
+        const int prow = (reg & 3) + 8 * (reg >> 2) + 4 * kgrp;
+        const float av = acc[reg];
+        const float sxv = Pstat[prow];
+        const float xm = Pstat[NCC_TP + prow];
+        const float denx = Pstat[2 * NCC_TP + prow];
+        const float num = av - ym * sxv - xm * syv + fK * xm * ym;
+        float val = num * __builtin_amdgcn_rsqf(fmaxf(denx * deny, NCC_EPS));
+        if (use_mask) {
+          const float dd = di - Pstat[3 * NCC_TP + prow];
+          const float dj = (float)(j + pw / 2 - 1) - Pstat[4 * NCC_TP + prow];
+          val *= __expf(-FOURLN2 * (dd * dd * ish2 + dj * dj * isw2));
+        }
+        unsigned long long key =
+            ((unsigned long long)nfloat_flip(val) << 32) |
+            (unsigned long long)(~idx);
+        key = (jvalid && (p0 + prow) < P) ? key : 0ull;
+        if (key > bestk[reg]) bestk[reg] = key;
+      }
     }
   };
 
@@ -542,6 +639,23 @@ void ncc_main_v2_kernel(const ncbf16* __restrict__ tx,
     if (colL == 0 && prow < P && k != 0ull) atomicMax(&best[prow], k);
   }
 }
+
+// the four instantiations the host wrapper launches (also what a standalone
+// compile of this file emits)
+#define NCC_MAIN_ARGS                                                        \
+  const ncbf16*, const ncbf16*, const unsigned int*, const unsigned short*, \
+      const float*, const float*, const float*, const float*,               \
+      unsigned long long*, int, int, int, int, int, int, int, int, int
+#define NCC_MAIN_V2_ARGS                                                   \
+  const ncbf16*, const ncbf16*, const unsigned int*, const float*,        \
+      const float*, const float*, const float*, unsigned long long*, int, \
+      int, int, int, int, int, int, int, int
+template __global__ void ncc_main_kernel<false>(NCC_MAIN_ARGS);
+template __global__ void ncc_main_kernel<true>(NCC_MAIN_ARGS);
+template __global__ void ncc_main_v2_kernel<false>(NCC_MAIN_V2_ARGS);
+template __global__ void ncc_main_v2_kernel<true>(NCC_MAIN_V2_ARGS);
+#undef NCC_MAIN_ARGS
+#undef NCC_MAIN_V2_ARGS
 
 // ---------------------------------------------------------------- stage 5
 

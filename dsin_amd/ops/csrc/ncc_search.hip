@@ -16,13 +16,20 @@
 // (evaluated inline, never materialized) and a packed-u64 atomic argmax with
 // TF tie semantics (smallest index wins) live in the epilogue. Device code in
 // ncc_kernels.h (torch-free, compilable standalone for .s inspection).
+//
+// L2+LAB mode (use_L2andLAB; reference src/siFinder.py:13-31, 102-103,
+// 145-195): the operands are the CIELAB transform of the raw images (bf16),
+// the score is the squared distance sum_x2 - 2*xy + sum_y2 times the same
+// prior, and the winner is the argmin, first index on ties. Same pipeline;
+// only the transform kernel and the main-kernel instantiation differ.
 
 #include "common.h"
 #include "ncc_kernels.h"
 
 namespace dsin {
 
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search(
+template <bool L2>
+static std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search_impl(
     torch::Tensor x_dec, torch::Tensor y_dec, torch::Tensor y_orig,
     int64_t ph_, int64_t pw_, bool use_mask) {
   CHECK_CUDA_CONTIG(x_dec);
@@ -65,9 +72,10 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search(
   auto t_y = torch::empty({(int64_t)3 * H * W + 192},
                           optsF.dtype(torch::kBFloat16));
   int64_t hw = (int64_t)H * W;
-  hipLaunchKernelGGL(transform_kernel, grid1d(hw, 256), dim3(256), 0, stream,
+  const auto transform = L2 ? lab_transform_kernel : transform_kernel;
+  hipLaunchKernelGGL(transform, grid1d(hw, 256), dim3(256), 0, stream,
                      x_dec.data_ptr<float>(), (ncbf16*)t_x.data_ptr(), hw);
-  hipLaunchKernelGGL(transform_kernel, grid1d(hw, 256), dim3(256), 0, stream,
+  hipLaunchKernelGGL(transform, grid1d(hw, 256), dim3(256), 0, stream,
                      y_dec.data_ptr<float>(), (ncbf16*)t_y.data_ptr(), hw);
 
   auto psum = torch::empty({P}, optsF);
@@ -94,7 +102,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search(
   dim3 grid((Wc + tj - 1) / tj, (Hc + NCC_TI - 1) / NCC_TI,
             (P + NCC_TP - 1) / NCC_TP);
   if (v2) {
-    hipLaunchKernelGGL(ncc_main_v2_kernel, grid, dim3(256), lds, stream,
+    hipLaunchKernelGGL(ncc_main_v2_kernel<L2>, grid, dim3(256), lds, stream,
                        (const ncbf16*)t_x.data_ptr(),
                        (const ncbf16*)t_y.data_ptr(),
                        (const unsigned int*)aoffs.data_ptr(),
@@ -103,7 +111,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search(
                        (unsigned long long*)best.data_ptr(), H, W, ph, pw,
                        gw, P, Hc, Wc, use_mask ? 1 : 0);
   } else {
-    hipLaunchKernelGGL(ncc_main_kernel, grid, dim3(256), lds, stream,
+    hipLaunchKernelGGL(ncc_main_kernel<L2>, grid, dim3(256), lds, stream,
                        (const ncbf16*)t_x.data_ptr(),
                        (const ncbf16*)t_y.data_ptr(),
                        (const unsigned int*)aoffs.data_ptr(),
@@ -118,7 +126,8 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search(
   {
     const hipError_t err = hipGetLastError();
     TORCH_CHECK(err == hipSuccess, "ncc_search: launch of ",
-                v2 ? "ncc_main_v2_kernel" : "ncc_main_kernel", " with ", lds,
+                v2 ? "ncc_main_v2_kernel" : "ncc_main_kernel",
+                L2 ? "<L2>" : "", " with ", lds,
                 " bytes of dynamic LDS failed: ", hipGetErrorString(err));
   }
 
@@ -132,6 +141,34 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search(
                      (long long*)cols.data_ptr<int64_t>(), H, W, ph, pw, gw, P,
                      Wc);
   return {y_syn, rows, cols};
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search(
+    torch::Tensor x_dec, torch::Tensor y_dec, torch::Tensor y_orig,
+    int64_t ph, int64_t pw, bool use_mask) {
+  return ncc_search_impl<false>(x_dec, y_dec, y_orig, ph, pw, use_mask);
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search_l2lab(
+    torch::Tensor x_dec, torch::Tensor y_dec, torch::Tensor y_orig,
+    int64_t ph, int64_t pw, bool use_mask) {
+  return ncc_search_impl<true>(x_dec, y_dec, y_orig, ph, pw, use_mask);
+}
+
+// The bf16 LAB operands of the L2+LAB search, (3,H,W) fp32 -> (3,H,W) bf16:
+// what the tests' oracle needs (the device powf/cbrtf are not bit-identical
+// to the host's).
+torch::Tensor ncc_lab_transform(torch::Tensor img) {
+  CHECK_CUDA_CONTIG(img);
+  TORCH_CHECK(img.dim() == 3 && img.size(0) == 3, "img must be (3,H,W)");
+  TORCH_CHECK(img.scalar_type() == torch::kFloat32, "img must be fp32");
+  auto out = torch::empty_like(img, img.options().dtype(torch::kBFloat16));
+  const int64_t hw = img.size(1) * img.size(2);
+  if (hw > 0)
+    hipLaunchKernelGGL(lab_transform_kernel, grid1d(hw, 256), dim3(256), 0,
+                       at::cuda::getCurrentCUDAStream(),
+                       img.data_ptr<float>(), (ncbf16*)out.data_ptr(), hw);
+  return out;
 }
 
 // MFMA layout self-check used by the GPU tests: C = A(16x32) @ B(32x16), bf16
