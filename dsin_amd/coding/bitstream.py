@@ -12,7 +12,7 @@ Container (little-endian, 22-byte header, then the payload):
 
     4s  magic  b"DSIN"
     B   version (1)
-    B   backend id (0 torch, 1 hip)
+    B   backend id (0 torch, 1 hip, 2 portable)
     H   C   bottleneck channels
     H   Hb  bottleneck height
     H   Wb  bottleneck width
@@ -21,12 +21,23 @@ Container (little-endian, 22-byte header, then the payload):
     I   payload length in bytes
     ..  payload: range-coded symbols in wave order
 
-The backend is hip when the model is on a GPU and torch on the CPU. The two
-do NOT decode each other's streams: the hip kernels evaluate the context
-model in fp32 with their own ``expf`` and scale tables by 65536-L, the torch
-path uses the torch convs (bf16 panels on a GPU) and a 65536 scale, so the
-frequency tables differ. A stream records its backend and ``decompress``
-refuses one it cannot reproduce.
+Without a ``backend`` argument ``compress`` picks hip when the model is on a
+GPU and torch on the CPU. Those two do NOT decode each other's streams: the
+hip kernels evaluate the context model in fp32 with their own ``expf`` and
+scale tables by 65536-L, the torch path uses the torch convs (bf16 panels on
+a GPU) and a 65536 scale, so the frequency tables differ. A stream records
+its backend and ``decompress`` refuses one it cannot reproduce: id 0 on a
+GPU model, id 1 on a CPU model.
+
+``compress(model, x, backend="portable")`` writes id 2, the stream to use
+when encoder and decoder are different machines. Its tables come from
+correctly rounded fp32 operations and integer arithmetic only
+(``ops/csrc/pc_model.h``, specified in ``docs/KERNELS.md``), which a gfx950
+kernel and the extension's host build evaluate to the same bits, so a
+portable stream written on a GPU decodes on a CPU model and the reverse.
+``decompress`` accepts id 2 on any device. (Only the symbols are portable:
+the decoder network's ``x_dec`` still differs in the last bits between a GPU
+and a CPU.)
 """
 
 from __future__ import annotations
@@ -41,7 +52,7 @@ from .entropy import decode_symbols, encode_symbols
 
 MAGIC = b"DSIN"
 VERSION = 1
-BACKEND_IDS = {"torch": 0, "hip": 1}
+BACKEND_IDS = {"torch": 0, "hip": 1, "portable": 2}
 _HEADER = struct.Struct("<4sBBHHHHII")
 HEADER_SIZE = _HEADER.size
 
@@ -109,8 +120,13 @@ def _as_batch(x: torch.Tensor, what: str) -> torch.Tensor:
 
 
 @torch.no_grad()
-def compress(model, x: torch.Tensor) -> bytes:
-    """Encode one image to a self-describing byte string."""
+def compress(model, x: torch.Tensor, backend: Optional[str] = None) -> bytes:
+    """Encode one image to a self-describing byte string. backend None is
+    the model's own (hip on a GPU, torch on the CPU); "portable" writes a
+    stream that any device decodes."""
+    if backend is not None and backend not in BACKEND_IDS:
+        raise ValueError(f"backend must be one of {tuple(BACKEND_IDS)}, got "
+                         f"{backend!r}")
     from ..ops import conv as _conv
     x = _as_batch(x, "x")
     _conv.begin_step()
@@ -118,7 +134,8 @@ def compress(model, x: torch.Tensor) -> bytes:
     z = model.encoder(x)
     symbols = z.symbols[0]
     centers = model.encoder.quantizer.centers.detach()
-    backend = model_backend(model)
+    if backend is None:
+        backend = model_backend(model)
     payload = encode_symbols(model.probclass, centers, symbols,
                              backend=backend)
     return pack_container(backend, symbols.shape, centers.numel(),
@@ -135,6 +152,8 @@ def decompress(model, data: bytes, y: Optional[torch.Tensor] = None
     from ..ops import conv as _conv
     bid, shape, L, crc, payload = parse_container(data)
     backend = model_backend(model)
+    if bid == BACKEND_IDS["portable"]:
+        backend = "portable"
     if bid != BACKEND_IDS[backend]:
         names = {v: k for k, v in BACKEND_IDS.items()}
         raise ValueError(

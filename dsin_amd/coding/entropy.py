@@ -135,7 +135,7 @@ def _gather_blocks(q_pad: torch.Tensor, wave: np.ndarray,
     return torch.stack(blocks)
 
 
-BACKENDS = ("torch", "hip")
+BACKENDS = ("torch", "hip", "portable")
 
 
 def _check_backend(backend: str) -> None:
@@ -152,16 +152,18 @@ def _torch_backend_cache_reset(device: torch.device) -> None:
         _conv.begin_step()
 
 
-def _hip_setup(pc: ProbClass, centers: torch.Tensor, shape, device):
+def _hip_setup(pc: ProbClass, centers: torch.Tensor, shape, device,
+               portable: bool = False):
     """Checks + the pad-filled value buffer, wave-ordered positions and wave
-    offsets shared by the hip encoder and decoder."""
+    offsets shared by the hip / portable encoder and decoder."""
     from .. import ops
     ops.check_pc_shape(pc)
-    if device.type != "cuda":
+    name = "portable" if portable else "hip"
+    if device.type != "cuda" and not portable:
         raise ValueError("backend='hip' needs the model and symbols on a GPU")
     C, H, W = (int(v) for v in shape)
     if min(C, H, W) < 1:
-        raise ValueError(f"backend='hip': empty symbol volume {shape}")
+        raise ValueError(f"backend={name!r}: empty symbol volume {shape}")
     pad = pc.context_size() // 2
     waves = _wave_order(C, H, W, pad)
     pos = torch.from_numpy(np.concatenate(waves).astype(np.int32)).to(device)
@@ -172,19 +174,24 @@ def _hip_setup(pc: ProbClass, centers: torch.Tensor, shape, device):
     return ops, pad, pos, offsets, q_pad
 
 
-def _encode_symbols_hip(pc, centers, symbols) -> bytes:
+def _encode_symbols_hip(pc, centers, symbols, portable=False) -> bytes:
     dev = centers.device
-    ops, pad, pos, _, q_pad = _hip_setup(pc, centers, symbols.shape, dev)
+    ops, pad, pos, _, q_pad = _hip_setup(pc, centers, symbols.shape, dev,
+                                         portable)
     sym = symbols.to(dev)
     C, H, W = sym.shape
     q_pad[pad:, pad:H + pad, pad:W + pad] = centers.float()[sym]
     p = pos.long()
-    return ops.pc_encode(pc, q_pad, pos, sym[p[:, 0], p[:, 1], p[:, 2]])
+    return ops.pc_encode(pc, q_pad, pos, sym[p[:, 0], p[:, 1], p[:, 2]],
+                         portable=portable)
 
 
-def _decode_symbols_hip(pc, centers, data, shape, device) -> torch.Tensor:
-    ops, _, pos, offsets, q_pad = _hip_setup(pc, centers, shape, device)
-    return ops.pc_decode(pc, q_pad, pos, offsets, data, centers)
+def _decode_symbols_hip(pc, centers, data, shape, device,
+                        portable=False) -> torch.Tensor:
+    ops, _, pos, offsets, q_pad = _hip_setup(pc, centers, shape, device,
+                                             portable)
+    return ops.pc_decode(pc, q_pad, pos, offsets, data, centers,
+                         portable=portable)
 
 
 @torch.no_grad()
@@ -197,6 +204,10 @@ def encode_symbols(pc: ProbClass, centers: torch.Tensor,
     two backends do not decode each other's streams: their tables differ
     (fp32 kernels and a 65536-L table scale against the torch convs and a
     65536 scale).
+    backend="portable": the specification of ops/csrc/pc_model.h, run by the
+    HIP kernels when centers are on a GPU and by the extension's host build
+    when they are on the CPU. Both give the same bytes and each decodes the
+    other's stream; "torch" and "hip" streams stay apart from it.
 
     Frequencies are computed through the SAME per-wave batched network
     calls the decoder runs — same batch shapes, same block contents at
@@ -207,8 +218,9 @@ def encode_symbols(pc: ProbClass, centers: torch.Tensor,
     streams sometimes fail to decode is worse than no fast path.)
     """
     _check_backend(backend)
-    if backend == "hip":
-        return _encode_symbols_hip(pc, centers, symbols)
+    if backend in ("hip", "portable"):
+        return _encode_symbols_hip(pc, centers, symbols,
+                                   portable=backend == "portable")
     sym = symbols.cpu().numpy()
     C, H, W = sym.shape
     pad = pc.context_size() // 2
@@ -246,12 +258,15 @@ def decode_symbols(pc: ProbClass, centers: torch.Tensor, data: bytes,
     inverse of encode_symbols with the same backend: one batched network
     call per skewed wave (O(25C + 5H + W) calls), then the wave's symbols
     are range-decoded sequentially against the batch's frequency tables.
-    backend="hip" keeps both steps on the GPU (ops.pc_decode)."""
+    backend="hip" keeps both steps on the GPU (ops.pc_decode);
+    backend="portable" does the same on a GPU and runs the host build on
+    the CPU, and decodes a portable stream written on either."""
     _check_backend(backend)
     C, H, W = shape
     device = torch.device(device or centers.device)
-    if backend == "hip":
-        return _decode_symbols_hip(pc, centers, data, shape, device)
+    if backend in ("hip", "portable"):
+        return _decode_symbols_hip(pc, centers, data, shape, device,
+                                   portable=backend == "portable")
     _torch_backend_cache_reset(device)
     pred = PredictionNetwork(pc, centers)
     pad = pc.context_size() // 2

@@ -8,6 +8,9 @@ GPU run can never accidentally measure the PyTorch path.
 
 CPU tensors always use the reference implementations in
 :mod:`dsin_amd.ops.reference` (also the numerics oracles for the GPU tests).
+The one exception is the portable entropy codec (``pc_*(portable=True)``),
+whose CPU side is a host build inside the same extension and raises in the
+same way when the extension is missing.
 """
 
 from __future__ import annotations
@@ -39,11 +42,11 @@ def hip_available() -> bool:
     return _try_load_ext() is not None
 
 
-def _require_ext(opname: str):
+def _require_ext(opname: str, where: str = "on a GPU tensor"):
     ext = _try_load_ext()
     if ext is None:
         raise RuntimeError(
-            f"dsin_amd op {opname!r} called on a GPU tensor but the HIP extension "
+            f"dsin_amd op {opname!r} called {where} but the HIP extension "
             f"is not built (import error: {_EXT_ERR}). Build it in-tree with "
             f"`python setup.py build_ext --inplace` (PYTORCH_ROCM_ARCH=gfx950).")
     if not hasattr(ext, opname):
@@ -366,6 +369,9 @@ def downsample2(x: torch.Tensor) -> torch.Tensor:
 # ---------------------------------------------------------------------------
 # Entropy codec: per-position probclass context model + device range coder.
 # HIP kernels: csrc/pc_codec.hip (step functions in csrc/rc_coder.h).
+# portable=True selects the backend-id-2 specification (csrc/pc_model.h):
+# HIP kernels on GPU tensors, the extension's host build on CPU tensors,
+# bit-identical logits, tables and bytes on both.
 # ---------------------------------------------------------------------------
 
 PC_MAX_K = 32
@@ -456,9 +462,31 @@ def pc_table_from_probs(p: torch.Tensor) -> torch.Tensor:
         torch.int32).clamp(min=1)
 
 
-def _pc_args(pc, q_pad: torch.Tensor, pos: torch.Tensor):
+def _pc_fn(name: str, q_pad: torch.Tensor):
+    """The extension entry for the device q_pad lives on (portable only on
+    the CPU); a missing extension is a RuntimeError on either."""
+    if q_pad.is_cuda:
+        return _require_ext(name)
+    return _require_ext(name + "_host",
+                        "for the portable codec on CPU tensors")
+
+
+def pc_host_fma_available() -> bool:
+    """Whether this CPU runs the portable host path with hardware FMA."""
+    return bool(_require_ext("pc_host_has_fma", "on the CPU")())
+
+
+def pc_host_force_libm(on: bool) -> bool:
+    """Force the portable host path through the C library's fmaf (True) or
+    return to the run-time choice (False); returns the previous setting.
+    Both paths give the same bits; this exists so a test can compare them."""
+    return bool(_require_ext("pc_host_force_libm", "on the CPU")(bool(on)))
+
+
+def _pc_args(pc, q_pad: torch.Tensor, pos: torch.Tensor,
+             portable: bool = False):
     k, L = check_pc_shape(pc)
-    if not q_pad.is_cuda:
+    if not q_pad.is_cuda and not portable:
         raise ValueError("pc codec: the hip backend needs GPU tensors")
     if q_pad.dim() != 3 or min(q_pad.shape[0] - 4, q_pad.shape[1] - 8,
                                q_pad.shape[2] - 8) < 1:
@@ -472,26 +500,34 @@ def _pc_args(pc, q_pad: torch.Tensor, pos: torch.Tensor):
 
 @torch.no_grad()
 def pc_freqs(pc, q_pad: torch.Tensor, pos: torch.Tensor,
-             packed: Optional[torch.Tensor] = None
+             packed: Optional[torch.Tensor] = None, portable: bool = False
              ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Context model at a list of positions of the padded value buffer:
-    (fp32 logits (n, L), int32 frequency tables (n, L)). GPU only."""
-    k, L, q_pad, pos = _pc_args(pc, q_pad, pos)
-    fn = _require_ext("pc_freqs")
+    (fp32 logits (n, L), int32 frequency tables (n, L)). GPU only, unless
+    portable=True, which also serves CPU tensors."""
+    k, L, q_pad, pos = _pc_args(pc, q_pad, pos, portable)
+    fn = _pc_fn("pc_freqs", q_pad)
     if packed is None:
         packed = pc_pack_weights(pc)
-    return fn(q_pad, pos, packed, k, L)
+    packed = packed.to(q_pad.device)
+    if not q_pad.is_cuda:
+        return fn(q_pad, pos, packed, k, L)
+    return fn(q_pad, pos, packed, k, L, portable)
 
 
 @torch.no_grad()
 def pc_encode(pc, q_pad: torch.Tensor, pos: torch.Tensor,
-              symbols: torch.Tensor) -> bytes:
-    """Range-code symbols (n,) at positions (n, 3) in the given order: one
-    pc_freqs launch, one rc_encode launch, one device-to-host copy."""
-    k, L, q_pad, pos = _pc_args(pc, q_pad, pos)
-    fn = _require_ext("pc_encode")
+              symbols: torch.Tensor, portable: bool = False) -> bytes:
+    """Range-code symbols (n,) at positions (n, 3) in the given order. GPU:
+    one pc_freqs launch, one rc_encode launch, one device-to-host copy.
+    CPU (portable only): the host build, same bytes."""
+    k, L, q_pad, pos = _pc_args(pc, q_pad, pos, portable)
+    fn = _pc_fn("pc_encode", q_pad)
     syms = symbols.to(device=q_pad.device, dtype=torch.int32).contiguous()
-    buf = fn(q_pad, pos, syms, pc_pack_weights(pc), k, L).cpu().numpy()
+    packed = pc_pack_weights(pc).to(q_pad.device)
+    if not q_pad.is_cuda:
+        return fn(q_pad, pos, syms, packed, k, L).numpy().tobytes()
+    buf = fn(q_pad, pos, syms, packed, k, L, portable).cpu().numpy()
     n = int.from_bytes(buf[:8].tobytes(), "little")
     if n > buf.size - 8:
         raise RuntimeError(f"pc_encode: stream of {n} bytes overran the "
@@ -501,19 +537,22 @@ def pc_encode(pc, q_pad: torch.Tensor, pos: torch.Tensor,
 
 @torch.no_grad()
 def pc_decode(pc, q_pad: torch.Tensor, pos: torch.Tensor, offsets,
-              data: bytes, centers: torch.Tensor) -> torch.Tensor:
+              data: bytes, centers: torch.Tensor,
+              portable: bool = False) -> torch.Tensor:
     """Wavefront decode: wave i is pos[offsets[i]:offsets[i+1]]. q_pad is
     filled in place with centers[symbol]; returns (C, H, W) int64 symbols.
     The wave loop runs in C++ (two launches per wave, no host sync)."""
-    k, L, q_pad_c, pos = _pc_args(pc, q_pad, pos)
+    k, L, q_pad_c, pos = _pc_args(pc, q_pad, pos, portable)
     if q_pad_c.data_ptr() != q_pad.data_ptr():
         raise ValueError("pc_decode: q_pad must be fp32 and contiguous")
-    fn = _require_ext("pc_decode")
+    fn = _pc_fn("pc_decode", q_pad)
     raw = torch.frombuffer(bytearray(data) if len(data) else bytearray(1),
                            dtype=torch.uint8)[:len(data)]
-    return fn(q_pad, pos, [int(o) for o in offsets], pc_pack_weights(pc), k,
-              L, raw.to(q_pad.device).contiguous(),
-              centers.detach().to(q_pad.device).float().contiguous())
+    args = (q_pad, pos, [int(o) for o in offsets],
+            pc_pack_weights(pc).to(q_pad.device), k, L,
+            raw.to(q_pad.device).contiguous(),
+            centers.detach().to(q_pad.device).float().contiguous())
+    return fn(*args) if not q_pad.is_cuda else fn(*args, portable)
 
 
 # re-exports used across the package

@@ -77,18 +77,32 @@ torch::Tensor down2_bwd(torch::Tensor g, int64_t H, int64_t W, bool bf16_out);
 std::tuple<torch::Tensor, torch::Tensor> pc_freqs(torch::Tensor q_pad,
                                                   torch::Tensor pos,
                                                   torch::Tensor wts, int64_t k,
-                                                  int64_t L);
+                                                  int64_t L, bool portable);
 torch::Tensor rc_encode(torch::Tensor syms, torch::Tensor freqs);
 torch::Tensor rc_decode(torch::Tensor data, torch::Tensor freqs);
 torch::Tensor pc_encode(torch::Tensor q_pad, torch::Tensor pos,
                         torch::Tensor syms, torch::Tensor wts, int64_t k,
-                        int64_t L);
+                        int64_t L, bool portable);
 torch::Tensor pc_decode(torch::Tensor q_pad, torch::Tensor pos,
                         std::vector<int64_t> offsets, torch::Tensor wts,
                         int64_t k, int64_t L, torch::Tensor data,
-                        torch::Tensor centers);
+                        torch::Tensor centers, bool portable);
 torch::Tensor rc_encode_host(torch::Tensor syms, torch::Tensor freqs);
 torch::Tensor rc_decode_host(torch::Tensor data, torch::Tensor freqs);
+std::tuple<torch::Tensor, torch::Tensor> pc_freqs_host(torch::Tensor q_pad,
+                                                       torch::Tensor pos,
+                                                       torch::Tensor wts,
+                                                       int64_t k, int64_t L);
+torch::Tensor pc_encode_host(torch::Tensor q_pad, torch::Tensor pos,
+                             torch::Tensor syms, torch::Tensor wts, int64_t k,
+                             int64_t L);
+torch::Tensor pc_decode_host(torch::Tensor q_pad, torch::Tensor pos,
+                             std::vector<int64_t> offsets, torch::Tensor wts,
+                             int64_t k, int64_t L, torch::Tensor data,
+                             torch::Tensor centers);
+bool pc_host_force_libm(bool on);
+std::string pc_host_path();
+bool pc_host_has_fma();
 }  // namespace dsin
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -132,13 +146,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("down2_fwd", &dsin::down2_fwd, "MS-SSIM dyadic downsample");
   m.def("down2_bwd", &dsin::down2_bwd, "MS-SSIM dyadic downsample adjoint");
   m.def("pc_freqs", &dsin::pc_freqs,
-        "probclass context model per position: (logits, frequency tables)");
+        "probclass context model per position: (logits, frequency tables)",
+        py::arg("q_pad"), py::arg("pos"), py::arg("wts"), py::arg("k"),
+        py::arg("L"), py::arg("portable") = false);
   m.def("rc_encode", &dsin::rc_encode, "device range encoder");
   m.def("rc_decode", &dsin::rc_decode, "device range decoder, given tables");
-  m.def("pc_encode", &dsin::pc_encode, "context model + range encoder");
-  m.def("pc_decode", &dsin::pc_decode, "wavefront context-model decoder");
+  m.def("pc_encode", &dsin::pc_encode, "context model + range encoder",
+        py::arg("q_pad"), py::arg("pos"), py::arg("syms"), py::arg("wts"),
+        py::arg("k"), py::arg("L"), py::arg("portable") = false);
+  m.def("pc_decode", &dsin::pc_decode, "wavefront context-model decoder",
+        py::arg("q_pad"), py::arg("pos"), py::arg("offsets"), py::arg("wts"),
+        py::arg("k"), py::arg("L"), py::arg("data"), py::arg("centers"),
+        py::arg("portable") = false);
   m.def("rc_encode_host", &dsin::rc_encode_host,
         "host build of the range-encoder step functions");
   m.def("rc_decode_host", &dsin::rc_decode_host,
         "host build of the range-decoder step functions");
+  m.def("pc_freqs_host", &dsin::pc_freqs_host,
+        "portable context model on CPU tensors: (logits, frequency tables)");
+  m.def("pc_encode_host", &dsin::pc_encode_host,
+        "portable context model + range encoder on CPU tensors");
+  m.def("pc_decode_host", &dsin::pc_decode_host,
+        "portable wavefront decoder on CPU tensors");
+  m.def("pc_host_force_libm", &dsin::pc_host_force_libm,
+        "force the library-fmaf host path; returns the previous setting");
+  m.def("pc_host_path", &dsin::pc_host_path,
+        "host path in use: 'fma' (hardware FMA) or 'libm'");
+  m.def("pc_host_has_fma", &dsin::pc_host_has_fma,
+        "whether this CPU has the hardware-FMA host path");
 }

@@ -29,9 +29,21 @@
 //
 // Tables: stabilised fp32 softmax, f = max(1, floor(p * (65536 - L))), so
 // tot <= 65535 and the coder's range / tot is never 0.
+//
+// PORTABLE instantiation (codec backend id 2): the same conv chain with the
+// ReLU and the table epilogue of pc_model.h, which a host build reproduces
+// bit for bit (pc_freqs_host / pc_encode_host / pc_decode_host below).
+
+#include <atomic>
+#include <functional>
+#include <string>
 
 #include "common.h"
+#include "pc_model.h"
 #include "rc_coder.h"
+
+// No expression in this file lets a multiply feed an add; keep it so.
+#pragma clang fp contract(off)
 
 namespace dsin {
 
@@ -66,7 +78,8 @@ template <> struct WVec<2> {
 // One masked VALID conv layer on LDS activations. in: [cin][Di*Hi*Wi],
 // out: [kp][Do*Ho*Wo]. A work item is (group of CG output channels, output
 // site); sites are the fast index so a wave reads consecutive LDS words.
-template <int CG, int NT, int Di, int Hi, int Wi, bool RELU, bool SKIP>
+template <bool PORTABLE, int CG, int NT, int Di, int Hi, int Wi, bool RELU,
+          bool SKIP>
 __device__ __forceinline__ void pc_layer(const float* in, float* out,
                                          const float* __restrict__ w,
                                          const float* __restrict__ b, int cin,
@@ -102,12 +115,13 @@ __device__ __forceinline__ void pc_layer(const float* in, float* out,
       float r = acc[j];
       if (SKIP)
         r += skip[(co0 + j) * PC_S0 + (d + 2) * 49 + (h + 2) * 7 + (x + 2)];
-      if (RELU) r = fmaxf(r, 0.f);
+      if (RELU) r = PORTABLE ? pc::relu(r) : fmaxf(r, 0.f);
       out[(co0 + j) * So + p] = r;
     }
   }
 }
 
+template <bool PORTABLE>
 __global__ void __launch_bounds__(PC_THREADS)
 pc_freqs_kernel(const float* __restrict__ q_pad, int C, int H, int W,
                 const int* __restrict__ pos, const float* __restrict__ wts,
@@ -119,6 +133,7 @@ pc_freqs_kernel(const float* __restrict__ q_pad, int C, int H, int W,
   __shared__ float s_a2[PC_MAX_K * PC_S2];
   __shared__ float s_part[PC_NT_OTHER * PC_MAX_L];
   __shared__ float s_lg[PC_MAX_L];
+  __shared__ uint32_t s_u[PC_MAX_L];  // PORTABLE table weights
 
   const int64_t b = blockIdx.x;
   const int tid = threadIdx.x;
@@ -144,14 +159,14 @@ pc_freqs_kernel(const float* __restrict__ q_pad, int C, int H, int W,
   const float* w3 = b2 + kp;
   const float* b3 = w3 + (size_t)PC_NT_OTHER * k * L;
   __syncthreads();
-  pc_layer<8, PC_NT_FIRST, 5, 9, 9, true, false>(s_in, s_a0, w0, b0, 1, kp,
-                                                 nullptr);
+  pc_layer<PORTABLE, 8, PC_NT_FIRST, 5, 9, 9, true, false>(
+      s_in, s_a0, w0, b0, 1, kp, nullptr);
   __syncthreads();
-  pc_layer<8, PC_NT_OTHER, 4, 7, 7, true, false>(s_a0, s_a1, w1, b1, k, kp,
-                                                 nullptr);
+  pc_layer<PORTABLE, 8, PC_NT_OTHER, 4, 7, 7, true, false>(
+      s_a0, s_a1, w1, b1, k, kp, nullptr);
   __syncthreads();
-  pc_layer<2, PC_NT_OTHER, 3, 5, 5, false, true>(s_a1, s_a2, w2, b2, k, kp,
-                                                 s_a0);
+  pc_layer<PORTABLE, 2, PC_NT_OTHER, 3, 5, 5, false, true>(
+      s_a1, s_a2, w2, b2, k, kp, s_a0);
   __syncthreads();
   // conv2: one output site; tap t of the 2x3x3 input is site t. Thread
   // (t, l) sums over ci, then thread l adds the 14 partials in tap order.
@@ -170,7 +185,20 @@ pc_freqs_kernel(const float* __restrict__ q_pad, int C, int H, int W,
     s_lg[tid] = acc;
   }
   __syncthreads();
-  if (tid < L) {
+  if (PORTABLE) {  // pc_model.h: the functions the host build runs
+    bool finite = true;
+    if (tid < L) {
+      float m;
+      finite = pc::table_max(s_lg, L, &m);
+      s_u[tid] = finite ? pc::table_weight(s_lg[tid], m) : 0u;
+    }
+    __syncthreads();
+    if (tid < L) {
+      const uint64_t S = pc::table_sum(s_u, L, finite);
+      logits[b * L + tid] = s_lg[tid];
+      freqs[b * L + tid] = pc::table_entry(s_u[tid], S, L);
+    }
+  } else if (tid < L) {
     float m = s_lg[0];
     for (int l = 1; l < L; ++l) m = fmaxf(m, s_lg[l]);
     float sum = 0.f;
@@ -336,12 +364,14 @@ static void pc_check(const torch::Tensor& q_pad, const torch::Tensor& pos,
 
 static void launch_pc_freqs(const torch::Tensor& q_pad, const int* pos,
                             int64_t n, const torch::Tensor& wts, int64_t k,
-                            int64_t L, float* logits, int* freqs) {
+                            int64_t L, float* logits, int* freqs,
+                            bool portable) {
   if (n == 0) return;
   const int C = (int)q_pad.size(0) - 4, H = (int)q_pad.size(1) - 8,
             W = (int)q_pad.size(2) - 8;
   const int kp = (int)((k + 7) / 8 * 8);
-  hipLaunchKernelGGL(pc_freqs_kernel, dim3((unsigned)n), dim3(PC_THREADS), 0,
+  auto kernel = portable ? pc_freqs_kernel<true> : pc_freqs_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(PC_THREADS), 0,
                      at::cuda::getCurrentCUDAStream(),
                      q_pad.data_ptr<float>(), C, H, W, pos,
                      wts.data_ptr<float>(), (int)k, kp, (int)L, logits, freqs);
@@ -350,13 +380,13 @@ static void launch_pc_freqs(const torch::Tensor& q_pad, const int* pos,
 std::tuple<torch::Tensor, torch::Tensor> pc_freqs(torch::Tensor q_pad,
                                                   torch::Tensor pos,
                                                   torch::Tensor wts, int64_t k,
-                                                  int64_t L) {
+                                                  int64_t L, bool portable) {
   pc_check(q_pad, pos, wts, k, L);
   const int64_t n = pos.size(0);
   auto logits = torch::empty({n, L}, q_pad.options());
   auto freqs = torch::empty({n, L}, pos.options());
   launch_pc_freqs(q_pad, pos.data_ptr<int>(), n, wts, k, L,
-                  logits.data_ptr<float>(), freqs.data_ptr<int>());
+                  logits.data_ptr<float>(), freqs.data_ptr<int>(), portable);
   return {logits, freqs};
 }
 
@@ -382,10 +412,10 @@ torch::Tensor rc_encode(torch::Tensor syms, torch::Tensor freqs) {
 
 torch::Tensor pc_encode(torch::Tensor q_pad, torch::Tensor pos,
                         torch::Tensor syms, torch::Tensor wts, int64_t k,
-                        int64_t L) {
+                        int64_t L, bool portable) {
   TORCH_CHECK(syms.dim() == 1 && syms.size(0) == pos.size(0),
               "pc_encode: one symbol per position");
-  auto lf = pc_freqs(q_pad, pos, wts, k, L);
+  auto lf = pc_freqs(q_pad, pos, wts, k, L, portable);
   return rc_encode(syms, std::get<1>(lf));
 }
 
@@ -428,7 +458,7 @@ torch::Tensor rc_decode(torch::Tensor data, torch::Tensor freqs) {
 torch::Tensor pc_decode(torch::Tensor q_pad, torch::Tensor pos,
                         std::vector<int64_t> offsets, torch::Tensor wts,
                         int64_t k, int64_t L, torch::Tensor data,
-                        torch::Tensor centers) {
+                        torch::Tensor centers, bool portable) {
   pc_check(q_pad, pos, wts, k, L);
   CHECK_CUDA_CONTIG(data);
   CHECK_CUDA_CONTIG(centers);
@@ -460,7 +490,7 @@ torch::Tensor pc_decode(torch::Tensor q_pad, torch::Tensor pos,
     const int64_t o = offsets[i - 1], nw = offsets[i] - o;
     if (nw == 0) continue;
     launch_pc_freqs(q_pad, p + 3 * o, nw, wts, k, L, logits.data_ptr<float>(),
-                    freqs.data_ptr<int>());
+                    freqs.data_ptr<int>(), portable);
     hipLaunchKernelGGL(rc_decode_wave_kernel, dim3(1), dim3(RC_CHUNK), 0,
                        stream,
                        reinterpret_cast<rc::State*>(state.data_ptr<int64_t>()),
@@ -524,6 +554,210 @@ torch::Tensor rc_decode_host(torch::Tensor data, torch::Tensor freqs) {
   for (int64_t i = 0; i < n; ++i) {
     rc::cumulate(fp + i * L, (int)L, cum);
     op[i] = rc::decode_cum(st, src, cum, (int)L);
+  }
+  return out;
+}
+
+// ---------------------------------------------------------------------------
+// Host build of the portable backend (CPU tensors): pc_model.h per position,
+// positions of a wave spread over at::parallel_for, the coder step functions
+// of rc_coder.h. A position's logits and table depend on nothing but q_pad
+// and the weights, so the thread count does not change them.
+// ---------------------------------------------------------------------------
+
+// at::parallel_for, compiled with OpenMP in host_parallel.cpp.
+void host_parallel_for(int64_t begin, int64_t end, int64_t grain,
+                       const std::function<void(int64_t, int64_t)>& f);
+
+struct PcHostArgs {
+  const float* q_pad;
+  int Hp, Wp;
+  const int* pos;
+  pc::Weights wts;
+  float* logits;  // (n, L), may be nullptr
+  int* freqs;     // (n, L)
+};
+
+template <class Fma>
+static __forceinline__ void pc_host_range_impl(const PcHostArgs& a, int64_t lo,
+                                               int64_t hi) {
+  pc::Scratch scratch;
+  float lg[pc::MAX_L];
+  const int L = a.wts.L;
+  for (int64_t i = lo; i < hi; ++i) {
+    pc::eval_position<Fma>(a.q_pad, a.Hp, a.Wp, a.pos[3 * i], a.pos[3 * i + 1],
+                           a.pos[3 * i + 2], a.wts, scratch, lg,
+                           a.freqs + i * L);
+    if (a.logits)
+      for (int l = 0; l < L; ++l) a.logits[i * L + l] = lg[l];
+  }
+}
+
+static void pc_host_range_libm(const PcHostArgs& a, int64_t lo, int64_t hi) {
+  pc_host_range_impl<pc::FmaLibm>(a, lo, hi);
+}
+
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+#define PC_HOST_HAS_HW_PATH 1
+// The same source compiled for AVX2 + FMA: every fmaf becomes one (vector)
+// FMA instruction, which rounds once as the library call does.
+__attribute__((target("avx2,fma"))) static void pc_host_range_hw(
+    const PcHostArgs& a, int64_t lo, int64_t hi) {
+  pc_host_range_impl<pc::FmaBuiltin>(a, lo, hi);
+}
+static bool pc_host_cpu_has_fma() {
+  return __builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2");
+}
+#else
+#define PC_HOST_HAS_HW_PATH 0
+static void pc_host_range_hw(const PcHostArgs& a, int64_t lo, int64_t hi) {
+  pc_host_range_libm(a, lo, hi);
+}
+static bool pc_host_cpu_has_fma() { return false; }
+#endif
+
+static std::atomic<bool> g_pc_host_force_libm{false};
+
+// Force the library-fmaf path (true) or return to the run-time choice
+// (false). Returns the previous setting.
+bool pc_host_force_libm(bool on) { return g_pc_host_force_libm.exchange(on); }
+
+// "fma" when the hardware-FMA path would run now, "libm" otherwise.
+std::string pc_host_path() {
+  return (pc_host_cpu_has_fma() && !g_pc_host_force_libm.load()) ? "fma"
+                                                                 : "libm";
+}
+
+bool pc_host_has_fma() { return pc_host_cpu_has_fma(); }
+
+static void pc_host_check(const torch::Tensor& q_pad, const torch::Tensor& pos,
+                          const torch::Tensor& wts, int64_t k, int64_t L) {
+  TORCH_CHECK(!q_pad.is_cuda() && !pos.is_cuda() && !wts.is_cuda() &&
+                  q_pad.is_contiguous() && pos.is_contiguous() &&
+                  wts.is_contiguous(),
+              "pc_codec host: CPU contiguous tensors");
+  TORCH_CHECK(k >= 1 && k <= PC_MAX_K, "pc_codec: k must be in [1, ",
+              PC_MAX_K, "]");
+  TORCH_CHECK(L >= 1 && L <= PC_MAX_L, "pc_codec: L must be in [1, ",
+              PC_MAX_L, "]");
+  TORCH_CHECK(q_pad.scalar_type() == torch::kFloat32 && q_pad.dim() == 3 &&
+                  q_pad.size(0) > 4 && q_pad.size(1) > 8 && q_pad.size(2) > 8,
+              "pc_codec: q_pad must be fp32 (C+4, H+8, W+8)");
+  TORCH_CHECK(pos.scalar_type() == torch::kInt32 && pos.dim() == 2 &&
+                  pos.size(1) == 3,
+              "pc_codec: positions must be int32 (n, 3)");
+  TORCH_CHECK(wts.scalar_type() == torch::kFloat32 &&
+                  wts.numel() == pc_packed_numel(k, L),
+              "pc_codec: packed weights have the wrong size");
+  const int C = (int)q_pad.size(0) - 4, H = (int)q_pad.size(1) - 8,
+            W = (int)q_pad.size(2) - 8;
+  const int* p = pos.data_ptr<int>();
+  for (int64_t i = 0; i < pos.size(0); ++i)
+    TORCH_CHECK(p[3 * i] >= 0 && p[3 * i] < C && p[3 * i + 1] >= 0 &&
+                    p[3 * i + 1] < H && p[3 * i + 2] >= 0 && p[3 * i + 2] < W,
+                "pc_codec host: position ", i, " outside the volume");
+}
+
+// Tables (and logits) of positions [lo, hi) of a.pos.
+static void pc_host_eval(const PcHostArgs& a, int64_t lo, int64_t hi) {
+  const bool hw = pc_host_cpu_has_fma() && !g_pc_host_force_libm.load();
+  host_parallel_for(lo, hi, 1, [&](int64_t b, int64_t e) {
+    if (hw)
+      pc_host_range_hw(a, b, e);
+    else
+      pc_host_range_libm(a, b, e);
+  });
+}
+
+static PcHostArgs pc_host_args(const torch::Tensor& q_pad,
+                               const torch::Tensor& pos,
+                               const torch::Tensor& wts, int64_t k, int64_t L,
+                               float* logits, int* freqs) {
+  return PcHostArgs{q_pad.data_ptr<float>(), (int)q_pad.size(1),
+                    (int)q_pad.size(2),      pos.data_ptr<int>(),
+                    pc::unpack(wts.data_ptr<float>(), (int)k, (int)L),
+                    logits,                  freqs};
+}
+
+std::tuple<torch::Tensor, torch::Tensor> pc_freqs_host(torch::Tensor q_pad,
+                                                       torch::Tensor pos,
+                                                       torch::Tensor wts,
+                                                       int64_t k, int64_t L) {
+  pc_host_check(q_pad, pos, wts, k, L);
+  const int64_t n = pos.size(0);
+  auto logits = torch::empty({n, L}, q_pad.options());
+  auto freqs = torch::empty({n, L}, pos.options());
+  pc_host_eval(pc_host_args(q_pad, pos, wts, k, L, logits.data_ptr<float>(),
+                            freqs.data_ptr<int>()),
+               0, n);
+  return {logits, freqs};
+}
+
+// The payload bytes (no length prefix).
+torch::Tensor pc_encode_host(torch::Tensor q_pad, torch::Tensor pos,
+                             torch::Tensor syms, torch::Tensor wts, int64_t k,
+                             int64_t L) {
+  pc_host_check(q_pad, pos, wts, k, L);
+  TORCH_CHECK(!syms.is_cuda() && syms.is_contiguous() &&
+                  syms.scalar_type() == torch::kInt32 && syms.dim() == 1 &&
+                  syms.size(0) == pos.size(0),
+              "pc_encode_host: int32 (n,) symbols, one per position");
+  const int64_t n = pos.size(0);
+  auto freqs = torch::empty({n, L}, pos.options());
+  pc_host_eval(pc_host_args(q_pad, pos, wts, k, L, nullptr,
+                            freqs.data_ptr<int>()),
+               0, n);
+  return rc_encode_host(syms, freqs);
+}
+
+// Wavefront decode on the host: wave i covers pos[offsets[i], offsets[i+1]).
+// q_pad is filled in place; returns the (C, H, W) int64 symbols.
+torch::Tensor pc_decode_host(torch::Tensor q_pad, torch::Tensor pos,
+                             std::vector<int64_t> offsets, torch::Tensor wts,
+                             int64_t k, int64_t L, torch::Tensor data,
+                             torch::Tensor centers) {
+  pc_host_check(q_pad, pos, wts, k, L);
+  TORCH_CHECK(!data.is_cuda() && data.is_contiguous() &&
+                  data.scalar_type() == torch::kUInt8 && data.dim() == 1,
+              "pc_decode_host: data must be CPU uint8 (len,)");
+  TORCH_CHECK(!centers.is_cuda() && centers.is_contiguous() &&
+                  centers.scalar_type() == torch::kFloat32 &&
+                  centers.numel() == L,
+              "pc_decode_host: centers must be CPU fp32 (L,)");
+  const int64_t n = pos.size(0);
+  TORCH_CHECK(offsets.size() >= 1 && offsets.front() == 0 &&
+                  offsets.back() == n,
+              "pc_decode_host: wave offsets must run from 0 to n");
+  for (size_t i = 1; i < offsets.size(); ++i)
+    TORCH_CHECK(offsets[i] >= offsets[i - 1],
+                "pc_decode_host: wave offsets must not decrease");
+  const int C = (int)q_pad.size(0) - 4, H = (int)q_pad.size(1) - 8,
+            W = (int)q_pad.size(2) - 8;
+  auto out = torch::zeros({C, H, W}, torch::kInt64);
+  if (n == 0) return out;
+  auto freqs = torch::empty({n, L}, pos.options());
+  const PcHostArgs a = pc_host_args(q_pad, pos, wts, k, L, nullptr,
+                                    freqs.data_ptr<int>());
+  const rc::ByteSource src{data.data_ptr<uint8_t>(), (uint64_t)data.numel()};
+  rc::State st;
+  rc::decode_start(st, src);
+  const int* p = pos.data_ptr<int>();
+  const int* fp = freqs.data_ptr<int>();
+  const float* cen = centers.data_ptr<float>();
+  float* q = q_pad.data_ptr<float>();
+  int64_t* o = out.data_ptr<int64_t>();
+  uint32_t cum[rc::MAX_L + 1];
+  for (size_t wv = 1; wv < offsets.size(); ++wv) {
+    const int64_t lo = offsets[wv - 1], hi = offsets[wv];
+    if (hi == lo) continue;
+    pc_host_eval(a, lo, hi);
+    for (int64_t i = lo; i < hi; ++i) {
+      rc::cumulate(fp + i * L, (int)L, cum);
+      const int s = rc::decode_cum(st, src, cum, (int)L);
+      const int c = p[3 * i], h = p[3 * i + 1], w = p[3 * i + 2];
+      o[((int64_t)c * H + h) * W + w] = s;
+      q[((int64_t)(c + 4) * (H + 8) + (h + 4)) * (W + 8) + (w + 4)] = cen[s];
+    }
   }
   return out;
 }

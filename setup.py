@@ -33,9 +33,12 @@ setup(
             name="dsin_amd.ops._dsin_hip",
             sources=sources,
             extra_compile_args={
-                "cxx": ["-O3", "-std=c++17"],
+                # -fopenmp: host_parallel.cpp runs at::parallel_for, which is
+                # a serial loop in a translation unit built without OpenMP
+                "cxx": ["-O3", "-std=c++17", "-fopenmp"],
                 "nvcc": ["-O3", "-std=c++17", "--offload-arch=gfx950"],
             },
+            extra_link_args=["-fopenmp"],
         )
     ],
     cmdclass={"build_ext": BuildExtension},

@@ -1,12 +1,14 @@
 """Compress a PNG to a .dsin byte stream and back.
 
-    python tools/codec.py compress   <checkpoint> <x.png> <out.dsin>
+    python tools/codec.py compress   [--backend portable] <checkpoint> <x.png> <out.dsin>
     python tools/codec.py decompress <checkpoint> <in.dsin> [--side y.png] <out.png>
 
 <checkpoint> is a directory written by training (it holds model.pt). The
 model runs on the GPU when there is one (hip codec backend) and on the CPU
 otherwise (torch backend); a stream is decoded by the backend that wrote
-it (see dsin_amd/coding/bitstream.py). With --side the decoder also runs
+it (see dsin_amd/coding/bitstream.py). compress --backend portable writes a
+stream that decodes on a GPU and on the CPU alike; decompress needs no flag,
+the stream names its backend. With --side the decoder also runs
 the side-information search and fusion and writes x_with_si; without it,
 x_dec. Image height and width must be multiples of 8, and with --side they
 must tile by the patch size (--patch HxW, default from the config or the
@@ -82,6 +84,10 @@ def main() -> None:
     ap.add_argument("--patch", default=None, help="side-info patch size HxW")
     sub = ap.add_subparsers(dest="cmd", required=True)
     c = sub.add_parser("compress")
+    c.add_argument("--backend", default=None,
+                   choices=["torch", "hip", "portable"],
+                   help="codec backend (default: hip on a GPU, torch on the "
+                        "CPU); portable streams decode on any device")
     c.add_argument("checkpoint")
     c.add_argument("image")
     c.add_argument("out")
@@ -100,7 +106,7 @@ def main() -> None:
         x = load_image(args.image, device)
         model = build_model(args, x.shape[1], x.shape[2], device)
         with cast:
-            data = compress(model, x)
+            data = compress(model, x, backend=args.backend)
         with open(args.out, "wb") as f:
             f.write(data)
         bpp = 8.0 * len(data) / (x.shape[1] * x.shape[2])
