@@ -38,17 +38,29 @@ portable stream written on a GPU decodes on a CPU model and the reverse.
 ``decompress`` accepts id 2 on any device. (Only the symbols are portable:
 the decoder network's ``x_dec`` still differs in the last bits between a GPU
 and a CPU.)
+
+Batches: ``compress_batch(model, x)`` takes ``x`` of shape (B,3,H,W) and
+returns a list of B byte strings, each a complete version-1 container of one
+image that ``decompress`` opens on its own; there is no multi-image
+container. ``decompress_batch(model, datas, y)`` takes such a list (from
+``compress_batch`` or from B ``compress`` calls) and returns batched
+``x_dec`` / ``x_with_si``. The containers of one batch must agree in backend
+id, ``(C, Hb, Wb)`` and ``L``. With the hip and portable backends the B
+symbol volumes are entropy-coded together by the batched kernels
+(``encode_symbols_batch`` / ``decode_symbols_batch``): the images share one
+wave loop and each has a range coder of its own.
 """
 
 from __future__ import annotations
 
 import struct
 import zlib
-from typing import Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from .entropy import decode_symbols, encode_symbols
+from .entropy import (decode_symbols, decode_symbols_batch, encode_symbols,
+                      encode_symbols_batch)
 
 MAGIC = b"DSIN"
 VERSION = 1
@@ -142,15 +154,9 @@ def compress(model, x: torch.Tensor, backend: Optional[str] = None) -> bytes:
                           probclass_crc(model), payload)
 
 
-@torch.no_grad()
-def decompress(model, data: bytes, y: Optional[torch.Tensor] = None
-               ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-    """-> (x_dec, x_with_si). x_with_si is None without a side image y or
-    for an AE-only model. Every header problem is a ValueError raised
-    before any network or kernel runs."""
-    from .. import ops
-    from ..ops import conv as _conv
-    bid, shape, L, crc, payload = parse_container(data)
+def _check_header(model, bid: int, shape, L: int, crc: int) -> str:
+    """The checks decompress makes on a parsed header; -> the backend that
+    decodes the stream on this model."""
     backend = model_backend(model)
     if bid == BACKEND_IDS["portable"]:
         backend = "portable"
@@ -170,6 +176,20 @@ def decompress(model, data: bytes, y: Optional[torch.Tensor] = None
     if crc != probclass_crc(model):
         raise ValueError("container: CRC mismatch, the stream was written "
                          "with other probclass weights or centers")
+    return backend
+
+
+@torch.no_grad()
+def decompress(model, data: bytes, y: Optional[torch.Tensor] = None
+               ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """-> (x_dec, x_with_si). x_with_si is None without a side image y or
+    for an AE-only model. Every header problem is a ValueError raised
+    before any network or kernel runs."""
+    from .. import ops
+    from ..ops import conv as _conv
+    bid, shape, L, crc, payload = parse_container(data)
+    backend = _check_header(model, bid, shape, L, crc)
+    centers = model.encoder.quantizer.centers.detach()
     if y is not None:
         y = _as_batch(y, "y")
     _conv.begin_step()
@@ -178,6 +198,81 @@ def decompress(model, data: bytes, y: Optional[torch.Tensor] = None
                              device=centers.device, backend=backend)
     qbar = centers.float()[symbols].unsqueeze(0)
     x_dec = model.decoder(qbar)
+    if y is None or model.ae_only:
+        return x_dec, None
+    y_dec = model.create_y_dec(y)
+    y_syn = model.sifinder(x_dec.float(), y.float(), y_dec.float())
+    cat = torch.cat([ops.kitti_normalize(x_dec),
+                     ops.kitti_normalize(y_syn.to(x_dec.dtype))], dim=1)
+    return x_dec, ops.kitti_denormalize(model.sinet(cat))
+
+
+def _as_images(x: torch.Tensor, what: str) -> torch.Tensor:
+    if x.dim() != 4 or x.shape[0] < 1 or x.shape[1] != 3:
+        raise ValueError(f"{what} must be (B,3,H,W) with B >= 1, got "
+                         f"{tuple(x.shape)}")
+    return x
+
+
+@torch.no_grad()
+def compress_batch(model, x: torch.Tensor, backend: Optional[str] = None
+                   ) -> List[bytes]:
+    """Encode B images (B,3,H,W) to B self-describing byte strings, each a
+    single-image container that decompress opens. One encoder pass over the
+    batch and one encode_symbols_batch call."""
+    if backend is not None and backend not in BACKEND_IDS:
+        raise ValueError(f"backend must be one of {tuple(BACKEND_IDS)}, got "
+                         f"{backend!r}")
+    from ..ops import conv as _conv
+    x = _as_images(x, "x")
+    _conv.begin_step()
+    model.eval()
+    symbols = model.encoder(x).symbols
+    centers = model.encoder.quantizer.centers.detach()
+    if backend is None:
+        backend = model_backend(model)
+    payloads = encode_symbols_batch(model.probclass, centers, symbols,
+                                    backend=backend)
+    crc = probclass_crc(model)
+    return [pack_container(backend, symbols.shape[1:], centers.numel(), crc,
+                           p) for p in payloads]
+
+
+@torch.no_grad()
+def decompress_batch(model, datas: Sequence[bytes],
+                     y: Optional[torch.Tensor] = None
+                     ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """-> (x_dec (B,3,H,W), x_with_si or None) from B single-image
+    containers; y is (B,3,H,W) when given. Every header problem, containers
+    that differ in backend id, (C, Hb, Wb) or L, and a y of another batch
+    size are ValueErrors raised before any network or kernel runs."""
+    from .. import ops
+    from ..ops import conv as _conv
+    datas = list(datas)
+    if len(datas) < 1:
+        raise ValueError("decompress_batch: empty batch")
+    parsed = [parse_container(d) for d in datas]
+    bid, shape, L = parsed[0][:3]
+    backend = _check_header(model, *parsed[0][:4])
+    for i, (bid_i, shape_i, L_i, crc_i, _) in enumerate(parsed[1:], 1):
+        _check_header(model, bid_i, shape_i, L_i, crc_i)
+        if (bid_i, shape_i, L_i) != (bid, shape, L):
+            raise ValueError(
+                f"container {i}: backend id {bid_i}, volume {shape_i}, "
+                f"L={L_i} differ from container 0 (backend id {bid}, volume "
+                f"{shape}, L={L}); one batch holds one kind of stream")
+    if y is not None:
+        y = _as_images(y, "y")
+        if y.shape[0] != len(datas):
+            raise ValueError(f"decompress_batch: {len(datas)} streams but y "
+                             f"holds {y.shape[0]} images")
+    centers = model.encoder.quantizer.centers.detach()
+    _conv.begin_step()
+    model.eval()
+    symbols = decode_symbols_batch(model.probclass, centers,
+                                   [p[4] for p in parsed], shape,
+                                   device=centers.device, backend=backend)
+    x_dec = model.decoder(centers.float()[symbols])
     if y is None or model.ae_only:
         return x_dec, None
     y_dec = model.create_y_dec(y)

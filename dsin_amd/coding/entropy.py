@@ -32,7 +32,7 @@ either config.
 
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -192,6 +192,79 @@ def _decode_symbols_hip(pc, centers, data, shape, device,
                                              portable)
     return ops.pc_decode(pc, q_pad, pos, offsets, data, centers,
                          portable=portable)
+
+
+def _encode_symbols_hip_batch(pc, centers, symbols,
+                              portable=False) -> List[bytes]:
+    dev = centers.device
+    ops, pad, pos, _, q1 = _hip_setup(pc, centers, symbols.shape[1:], dev,
+                                      portable)
+    sym = symbols.to(dev)
+    B, C, H, W = sym.shape
+    q_pad = q1.unsqueeze(0).repeat(B, 1, 1, 1)
+    q_pad[:, pad:, pad:H + pad, pad:W + pad] = centers.float()[sym]
+    p = pos.long()
+    return ops.pc_encode_batch(pc, q_pad, pos,
+                               sym[:, p[:, 0], p[:, 1], p[:, 2]],
+                               portable=portable)
+
+
+def _decode_symbols_hip_batch(pc, centers, datas, shape, device,
+                              portable=False) -> torch.Tensor:
+    ops, _, pos, offsets, q1 = _hip_setup(pc, centers, shape, device,
+                                          portable)
+    q_pad = q1.unsqueeze(0).repeat(len(datas), 1, 1, 1)
+    return ops.pc_decode_batch(pc, q_pad, pos, offsets, datas, centers,
+                               portable=portable)
+
+
+@torch.no_grad()
+def encode_symbols_batch(pc: ProbClass, centers: torch.Tensor,
+                         symbols: torch.Tensor, backend: str = "torch"
+                         ) -> List[bytes]:
+    """symbols: (B, C, H, W) int64 -> B byte streams; element b is what
+    encode_symbols gives for symbols[b] with the same backend, so either
+    decoder reads it. "hip" and "portable" code the whole batch in one pass
+    of the batched kernels (ops.pc_encode_batch): the images share the wave
+    schedule and each has a range coder of its own. "torch" loops over the
+    images. An empty batch is a ValueError."""
+    _check_backend(backend)
+    if symbols.dim() != 4:
+        raise ValueError(f"encode_symbols_batch: symbols must be (B, C, H, "
+                         f"W), got {tuple(symbols.shape)}")
+    if symbols.shape[0] < 1:
+        raise ValueError("encode_symbols_batch: empty batch")
+    if backend in ("hip", "portable"):
+        return _encode_symbols_hip_batch(pc, centers, symbols,
+                                         portable=backend == "portable")
+    return [encode_symbols(pc, centers, s, backend=backend) for s in symbols]
+
+
+@torch.no_grad()
+def decode_symbols_batch(pc: ProbClass, centers: torch.Tensor,
+                         datas: Sequence[bytes],
+                         shape: Tuple[int, int, int],
+                         device: Optional[torch.device] = None,
+                         backend: str = "torch") -> torch.Tensor:
+    """Inverse of encode_symbols_batch: B streams of one (C, H, W) shape ->
+    (B, C, H, W) int64. The streams may come from encode_symbols_batch or
+    from B encode_symbols calls. "hip" and "portable" decode all images in
+    one wave loop (ops.pc_decode_batch: one state init plus two launches per
+    wave for any B); "torch" loops over the images. A short stream decodes
+    as decode_symbols decodes it, reading zeros past its own end."""
+    _check_backend(backend)
+    datas = list(datas)
+    if len(datas) < 1:
+        raise ValueError("decode_symbols_batch: empty batch")
+    if len(shape) != 3:
+        raise ValueError(f"decode_symbols_batch: shape must be (C, H, W), "
+                         f"got {tuple(shape)}")
+    device = torch.device(device or centers.device)
+    if backend in ("hip", "portable"):
+        return _decode_symbols_hip_batch(pc, centers, datas, shape, device,
+                                         portable=backend == "portable")
+    return torch.stack([decode_symbols(pc, centers, d, shape, device=device,
+                                       backend=backend) for d in datas])
 
 
 @torch.no_grad()

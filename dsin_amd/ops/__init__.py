@@ -15,7 +15,7 @@ same way when the extension is missing.
 
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -551,6 +551,110 @@ def pc_decode(pc, q_pad: torch.Tensor, pos: torch.Tensor, offsets,
     args = (q_pad, pos, [int(o) for o in offsets],
             pc_pack_weights(pc).to(q_pad.device), k, L,
             raw.to(q_pad.device).contiguous(),
+            centers.detach().to(q_pad.device).float().contiguous())
+    return fn(*args) if not q_pad.is_cuda else fn(*args, portable)
+
+
+# Batch forms: B images of one symbol-volume shape share the position list
+# and the wave schedule; q_pad is (B, C+4, H+8, W+8). The kernels are the
+# ones above with an image dimension (the calls above are their B = 1 case).
+
+PC_MAX_BATCH = 65535  # images per launch: the kernels' gridDim.y
+
+
+def _pc_batch_args(pc, q_pad: torch.Tensor, pos: torch.Tensor,
+                   portable: bool = False):
+    k, L = check_pc_shape(pc)
+    if not q_pad.is_cuda and not portable:
+        raise ValueError("pc codec: the hip backend needs GPU tensors")
+    if q_pad.dim() != 4 or q_pad.shape[0] < 1 or min(
+            q_pad.shape[1] - 4, q_pad.shape[2] - 8, q_pad.shape[3] - 8) < 1:
+        raise ValueError(f"pc codec: a batched q_pad must be "
+                         f"(B>=1, C+4, H+8, W+8), got {tuple(q_pad.shape)}")
+    if q_pad.shape[0] > PC_MAX_BATCH:
+        raise ValueError(f"pc codec: a batch of {q_pad.shape[0]} images is "
+                         f"above the {PC_MAX_BATCH} one call codes; split it")
+    if pos.dim() != 2 or pos.shape[1] != 3:
+        raise ValueError("pc codec: positions must be (n, 3)")
+    return (k, L, q_pad.float().contiguous(),
+            pos.to(device=q_pad.device, dtype=torch.int32).contiguous())
+
+
+@torch.no_grad()
+def pc_freqs_batch(pc, q_pad: torch.Tensor, pos: torch.Tensor,
+                   packed: Optional[torch.Tensor] = None,
+                   portable: bool = False
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """pc_freqs over a batch: q_pad (B, C+4, H+8, W+8), positions (n, 3)
+    shared by all images -> (fp32 logits (B, n, L), int32 tables (B, n, L)),
+    one launch on the GPU. [b] equals pc_freqs of image b alone, bit for
+    bit."""
+    k, L, q_pad, pos = _pc_batch_args(pc, q_pad, pos, portable)
+    fn = _pc_fn("pc_freqs_batch", q_pad)
+    if packed is None:
+        packed = pc_pack_weights(pc)
+    packed = packed.to(q_pad.device)
+    if not q_pad.is_cuda:
+        return fn(q_pad, pos, packed, k, L)
+    return fn(q_pad, pos, packed, k, L, portable)
+
+
+@torch.no_grad()
+def pc_encode_batch(pc, q_pad: torch.Tensor, pos: torch.Tensor,
+                    symbols: torch.Tensor, portable: bool = False
+                    ) -> List[bytes]:
+    """Range-code symbols (B, n) at positions (n, 3): one stream per image,
+    the bytes pc_encode gives for that image alone. GPU: one pc_freqs launch
+    over (positions, images), one rc_encode launch with a workgroup per
+    image, one device-to-host copy for the whole batch."""
+    k, L, q_pad, pos = _pc_batch_args(pc, q_pad, pos, portable)
+    if symbols.dim() != 2 or symbols.shape != (q_pad.shape[0], pos.shape[0]):
+        raise ValueError(f"pc_encode_batch: symbols must be (B, n) = "
+                         f"{(q_pad.shape[0], pos.shape[0])}, got "
+                         f"{tuple(symbols.shape)}")
+    fn = _pc_fn("pc_encode_batch", q_pad)
+    syms = symbols.to(device=q_pad.device, dtype=torch.int32).contiguous()
+    packed = pc_pack_weights(pc).to(q_pad.device)
+    if not q_pad.is_cuda:
+        buf = fn(q_pad, pos, syms, packed, k, L).numpy()
+    else:
+        buf = fn(q_pad, pos, syms, packed, k, L, portable).cpu().numpy()
+    out = []
+    for b in range(buf.shape[0]):
+        n = int.from_bytes(buf[b, :8].tobytes(), "little")
+        if n > buf.shape[1] - 8:
+            raise RuntimeError(
+                f"pc_encode_batch: stream {b} of {n} bytes overran its "
+                f"{buf.shape[1] - 8}-byte buffer")
+        out.append(buf[b, 8:8 + n].tobytes())
+    return out
+
+
+@torch.no_grad()
+def pc_decode_batch(pc, q_pad: torch.Tensor, pos: torch.Tensor, offsets,
+                    datas: Sequence[bytes], centers: torch.Tensor,
+                    portable: bool = False) -> torch.Tensor:
+    """Wavefront decode of B streams into q_pad (B, C+4, H+8, W+8), filled
+    in place; returns (B, C, H, W) int64 symbols. The payloads travel
+    concatenated with B+1 offsets, and each image's coder reads zeros past
+    the end of its own payload. One state init plus two launches per wave
+    for any B, issued from C++ without a host sync."""
+    k, L, q_pad_c, pos = _pc_batch_args(pc, q_pad, pos, portable)
+    if q_pad_c.data_ptr() != q_pad.data_ptr():
+        raise ValueError("pc_decode_batch: q_pad must be fp32 and contiguous")
+    if len(datas) != q_pad.shape[0]:
+        raise ValueError(f"pc_decode_batch: {len(datas)} streams for a batch "
+                         f"of {q_pad.shape[0]}")
+    fn = _pc_fn("pc_decode_batch", q_pad)
+    blob = b"".join(datas)
+    data_offs = [0]
+    for d in datas:
+        data_offs.append(data_offs[-1] + len(d))
+    raw = torch.frombuffer(bytearray(blob) if len(blob) else bytearray(1),
+                           dtype=torch.uint8)[:len(blob)]
+    args = (q_pad, pos, [int(o) for o in offsets],
+            pc_pack_weights(pc).to(q_pad.device), k, L,
+            raw.to(q_pad.device).contiguous(), data_offs,
             centers.detach().to(q_pad.device).float().contiguous())
     return fn(*args) if not q_pad.is_cuda else fn(*args, portable)
 

@@ -100,6 +100,30 @@ torch::Tensor pc_decode_host(torch::Tensor q_pad, torch::Tensor pos,
                              std::vector<int64_t> offsets, torch::Tensor wts,
                              int64_t k, int64_t L, torch::Tensor data,
                              torch::Tensor centers);
+std::tuple<torch::Tensor, torch::Tensor> pc_freqs_batch(
+    torch::Tensor q_pad, torch::Tensor pos, torch::Tensor wts, int64_t k,
+    int64_t L, bool portable);
+torch::Tensor rc_encode_batch(torch::Tensor syms, torch::Tensor freqs);
+torch::Tensor pc_encode_batch(torch::Tensor q_pad, torch::Tensor pos,
+                              torch::Tensor syms, torch::Tensor wts,
+                              int64_t k, int64_t L, bool portable);
+torch::Tensor pc_decode_batch(torch::Tensor q_pad, torch::Tensor pos,
+                              std::vector<int64_t> offsets, torch::Tensor wts,
+                              int64_t k, int64_t L, torch::Tensor data,
+                              std::vector<int64_t> data_offs,
+                              torch::Tensor centers, bool portable);
+std::tuple<torch::Tensor, torch::Tensor> pc_freqs_batch_host(
+    torch::Tensor q_pad, torch::Tensor pos, torch::Tensor wts, int64_t k,
+    int64_t L);
+torch::Tensor pc_encode_batch_host(torch::Tensor q_pad, torch::Tensor pos,
+                                   torch::Tensor syms, torch::Tensor wts,
+                                   int64_t k, int64_t L);
+torch::Tensor pc_decode_batch_host(torch::Tensor q_pad, torch::Tensor pos,
+                                   std::vector<int64_t> offsets,
+                                   torch::Tensor wts, int64_t k, int64_t L,
+                                   torch::Tensor data,
+                                   std::vector<int64_t> data_offs,
+                                   torch::Tensor centers);
 bool pc_host_force_libm(bool on);
 std::string pc_host_path();
 bool pc_host_has_fma();
@@ -168,6 +192,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "portable context model + range encoder on CPU tensors");
   m.def("pc_decode_host", &dsin::pc_decode_host,
         "portable wavefront decoder on CPU tensors");
+  m.def("pc_freqs_batch", &dsin::pc_freqs_batch,
+        "pc_freqs over (B, C+4, H+8, W+8): (B, n, L) logits and tables",
+        py::arg("q_pad"), py::arg("pos"), py::arg("wts"), py::arg("k"),
+        py::arg("L"), py::arg("portable") = false);
+  m.def("rc_encode_batch", &dsin::rc_encode_batch,
+        "device range encoder, one workgroup per image");
+  m.def("pc_encode_batch", &dsin::pc_encode_batch,
+        "context model + range encoder over a batch of images",
+        py::arg("q_pad"), py::arg("pos"), py::arg("syms"), py::arg("wts"),
+        py::arg("k"), py::arg("L"), py::arg("portable") = false);
+  m.def("pc_decode_batch", &dsin::pc_decode_batch,
+        "wavefront decoder over a batch of images, concatenated payloads",
+        py::arg("q_pad"), py::arg("pos"), py::arg("offsets"), py::arg("wts"),
+        py::arg("k"), py::arg("L"), py::arg("data"), py::arg("data_offs"),
+        py::arg("centers"), py::arg("portable") = false);
+  m.def("pc_freqs_batch_host", &dsin::pc_freqs_batch_host,
+        "portable context model over a batch of CPU images");
+  m.def("pc_encode_batch_host", &dsin::pc_encode_batch_host,
+        "portable context model + range encoder over a batch of CPU images");
+  m.def("pc_decode_batch_host", &dsin::pc_decode_batch_host,
+        "portable wavefront decoder over a batch of CPU images");
   m.def("pc_host_force_libm", &dsin::pc_host_force_libm,
         "force the library-fmaf host path; returns the previous setting");
   m.def("pc_host_path", &dsin::pc_host_path,

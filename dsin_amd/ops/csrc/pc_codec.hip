@@ -2,10 +2,14 @@
 // position (pc_freqs) and a range coder that never leaves the GPU
 // (rc_encode / rc_decode_wave).
 //
-// pc_freqs: one workgroup per queried position (c, h, w). The position's
-// 5x9x9 causal context is read from the padded value buffer q_pad
-// (C+4, H+8, W+8) and pushed through the four masked VALID 3-D convs in the
-// order ProbClass.logits uses:
+// Every kernel takes a batch of B images of one symbol-volume shape: the
+// value buffer is (B, C+4, H+8, W+8), the position list is shared, and the
+// single-image entry points are the B = 1 case of the same kernels.
+//
+// pc_freqs: one workgroup per (queried position (c, h, w), image); the image
+// is blockIdx.y. The position's 5x9x9 causal context is read from the padded
+// value buffer q_pad (C+4, H+8, W+8) of its image and pushed through the
+// four masked VALID 3-D convs in the order ProbClass.logits uses:
 //   conv0 +ReLU  1 -> k   5x9x9 -> 4x7x7
 //   res_conv1 +ReLU k -> k 4x7x7 -> 3x5x5
 //   res_conv2 + conv0[:, 2:, 2:-2, 2:-2]   3x5x5 -> 2x3x3
@@ -14,9 +18,9 @@
 // are read from global memory / L2, every workgroup reads the same ones.
 // fp32 operands, fp32 FMA accumulation. Every output element is produced by
 // exactly one thread looping (tap, ci) in a fixed order, so a position's
-// logits and table do not depend on what else is in the launch: the encoder
-// (one launch over all positions) and the decoder (one launch per wave)
-// produce bit-identical tables by construction.
+// logits and table do not depend on what else is in the launch, other
+// images included: the encoder (one launch over all positions) and the
+// decoder (one launch per wave) produce bit-identical tables by construction.
 //
 // Masks are structural. In the flattened (d, kh, kw) order of the 2x3x3
 // filter the live taps are exactly the first 13 (first_mask) or 14
@@ -39,6 +43,7 @@
 #include <string>
 
 #include "common.h"
+#include "pc_batch_host.h"
 #include "pc_model.h"
 #include "rc_coder.h"
 
@@ -49,6 +54,7 @@ namespace dsin {
 
 constexpr int PC_MAX_K = 32;
 constexpr int PC_MAX_L = rc::MAX_L;
+constexpr int PC_MAX_B = 65535;  // images per launch: gridDim.y
 constexpr int PC_THREADS = 256;
 constexpr int PC_NT_FIRST = 13;
 constexpr int PC_NT_OTHER = 14;
@@ -123,10 +129,10 @@ __device__ __forceinline__ void pc_layer(const float* in, float* out,
 
 template <bool PORTABLE>
 __global__ void __launch_bounds__(PC_THREADS)
-pc_freqs_kernel(const float* __restrict__ q_pad, int C, int H, int W,
-                const int* __restrict__ pos, const float* __restrict__ wts,
-                int k, int kp, int L, float* __restrict__ logits,
-                int* __restrict__ freqs) {
+pc_freqs_kernel(const float* __restrict__ q_pad, int64_t q_stride, int C,
+                int H, int W, const int* __restrict__ pos,
+                const float* __restrict__ wts, int k, int kp, int L,
+                float* __restrict__ logits, int* __restrict__ freqs) {
   __shared__ float s_in[PC_SIN + 3];
   __shared__ float s_a0[PC_MAX_K * PC_S0];
   __shared__ float s_a1[PC_MAX_K * PC_S1];
@@ -135,9 +141,12 @@ pc_freqs_kernel(const float* __restrict__ q_pad, int C, int H, int W,
   __shared__ float s_lg[PC_MAX_L];
   __shared__ uint32_t s_u[PC_MAX_L];  // PORTABLE table weights
 
-  const int64_t b = blockIdx.x;
+  // position blockIdx.x of image blockIdx.y; outputs are (B, n, L)
+  const int64_t ip = blockIdx.x;
+  const int64_t b = (int64_t)blockIdx.y * gridDim.x + ip;
   const int tid = threadIdx.x;
-  const int c = pos[3 * b], h = pos[3 * b + 1], w = pos[3 * b + 2];
+  const int c = pos[3 * ip], h = pos[3 * ip + 1], w = pos[3 * ip + 2];
+  q_pad += (int64_t)blockIdx.y * q_stride;
   if (c < 0 || c >= C || h < 0 || h >= H || w < 0 || w >= W) {
     if (tid < L) {  // never reached through the Python wrappers
       logits[b * L + tid] = 0.f;
@@ -220,12 +229,17 @@ pc_freqs_kernel(const float* __restrict__ q_pad, int C, int H, int W,
 constexpr int RC_CHUNK = 256;
 constexpr int RC_WIN = RC_CHUNK * rc::MAX_SHIFTS;  // bytes a chunk can read
 
-// out: 8 bytes little-endian payload length, then the payload (cap bytes).
+// One workgroup per image: syms (B, n), freqs (B, n, L), out (B, 8 + cap).
+// Row b of out: 8 bytes little-endian payload length, then the payload (cap
+// bytes).
 __global__ void __launch_bounds__(RC_CHUNK)
 rc_encode_kernel(const int* __restrict__ syms, const int* __restrict__ freqs,
                  int64_t n, int L, uint8_t* __restrict__ out, uint64_t cap) {
   __shared__ uint32_t s_cum[RC_CHUNK], s_f[RC_CHUNK], s_tot[RC_CHUNK];
   const int tid = threadIdx.x;
+  syms += (int64_t)blockIdx.x * n;
+  freqs += (int64_t)blockIdx.x * n * L;
+  out += (int64_t)blockIdx.x * (8 + cap);
   rc::State st;
   rc::init(st);
   const rc::ByteSink sink{out + 8, cap};
@@ -258,13 +272,25 @@ rc_encode_kernel(const int* __restrict__ syms, const int* __restrict__ freqs,
   }
 }
 
+// The payload of image b: data[offs[b], offs[b+1]) of the concatenated
+// buffer, or all len bytes when offs is null (a single image).
+__device__ __forceinline__ rc::ByteSource rc_image_bytes(
+    const uint8_t* data, uint64_t len, const int64_t* offs, int64_t b) {
+  if (offs == nullptr) return rc::ByteSource{data, len};
+  return rc::ByteSource{data + offs[b], (uint64_t)(offs[b + 1] - offs[b])};
+}
+
+// One thread per image starts that image's decoder state.
 __global__ void rc_decode_init_kernel(rc::State* state,
                                       const uint8_t* __restrict__ data,
-                                      uint64_t len) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
+                                      uint64_t len,
+                                      const int64_t* __restrict__ offs,
+                                      int64_t B) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) {
     rc::State st;
-    rc::decode_start(st, rc::ByteSource{data, len});
-    *state = st;
+    rc::decode_start(st, rc_image_bytes(data, len, offs, b));
+    state[b] = st;
   }
 }
 
@@ -280,21 +306,35 @@ struct WindowSource {
   }
 };
 
-// Decodes nw symbols against freqs (nw, L), advancing *state. With pos set,
-// symbol i goes to out[c, h, w] and centers[s] into q_pad at that position;
-// with pos == nullptr it goes to out[i].
+// One workgroup per image b = blockIdx.x: decodes nw symbols against
+// freqs[b] of (B, nw, L), advancing state[b]. The image's bytes are its own
+// slice of data (rc_image_bytes), so the window and every later read are
+// bounded by that image's payload: past its end the coder reads 0, never the
+// next image's first bytes. With pos set, symbol i goes to out[b, c, h, w]
+// and centers[s] into q_pad[b] at that position; with pos == nullptr it goes
+// to out[b, i] (out_stride = nw).
 __global__ void __launch_bounds__(RC_CHUNK)
-rc_decode_wave_kernel(rc::State* state, const uint8_t* __restrict__ data,
-                      uint64_t len, const int* __restrict__ freqs,
+rc_decode_wave_kernel(rc::State* state, const uint8_t* __restrict__ data_all,
+                      uint64_t len_all, const int64_t* __restrict__ offs,
+                      const int* __restrict__ freqs,
                       const int* __restrict__ pos, int64_t nw, int L,
                       const float* __restrict__ centers,
-                      float* __restrict__ q_pad, int C, int H, int W,
-                      int64_t* __restrict__ out) {
+                      float* __restrict__ q_pad, int64_t q_stride, int C,
+                      int H, int W, int64_t* __restrict__ out,
+                      int64_t out_stride) {
   __shared__ uint32_t s_cum[RC_CHUNK * (rc::MAX_L + 1)];
   __shared__ uint8_t s_win[RC_WIN];
   __shared__ int s_sym[RC_CHUNK];
   __shared__ rc::State s_state;
   const int tid = threadIdx.x;
+  const int64_t img = blockIdx.x;
+  const rc::ByteSource bytes = rc_image_bytes(data_all, len_all, offs, img);
+  const uint8_t* data = bytes.buf;
+  const uint64_t len = bytes.len;
+  state += img;
+  freqs += img * nw * L;
+  out += img * out_stride;
+  if (pos != nullptr) q_pad += img * q_stride;
   if (tid == 0) s_state = *state;
   __syncthreads();
   for (int64_t base = 0; base < nw; base += RC_CHUNK) {
@@ -351,9 +391,14 @@ static void pc_check(const torch::Tensor& q_pad, const torch::Tensor& pos,
               PC_MAX_K, "]");
   TORCH_CHECK(L >= 1 && L <= PC_MAX_L, "pc_codec: L must be in [1, ",
               PC_MAX_L, "]");
-  TORCH_CHECK(q_pad.scalar_type() == torch::kFloat32 && q_pad.dim() == 3 &&
-                  q_pad.size(0) > 4 && q_pad.size(1) > 8 && q_pad.size(2) > 8,
-              "pc_codec: q_pad must be fp32 (C+4, H+8, W+8)");
+  // (C+4, H+8, W+8), or (B, C+4, H+8, W+8) for the batch entry points
+  const int64_t d = q_pad.dim();
+  TORCH_CHECK(q_pad.scalar_type() == torch::kFloat32 && (d == 3 || d == 4) &&
+                  q_pad.size(d - 3) > 4 && q_pad.size(d - 2) > 8 &&
+                  q_pad.size(d - 1) > 8,
+              "pc_codec: q_pad must be fp32 ([B,] C+4, H+8, W+8)");
+  TORCH_CHECK(d == 3 || (q_pad.size(0) >= 1 && q_pad.size(0) <= PC_MAX_B),
+              "pc_codec: batch size must be in [1, ", PC_MAX_B, "]");
   TORCH_CHECK(pos.scalar_type() == torch::kInt32 && pos.dim() == 2 &&
                   pos.size(1) == 3,
               "pc_codec: positions must be int32 (n, 3)");
@@ -362,52 +407,86 @@ static void pc_check(const torch::Tensor& q_pad, const torch::Tensor& pos,
               "pc_codec: packed weights have the wrong size");
 }
 
+// q_pad is (B, C+4, H+8, W+8); logits and freqs are (B, n, L).
 static void launch_pc_freqs(const torch::Tensor& q_pad, const int* pos,
                             int64_t n, const torch::Tensor& wts, int64_t k,
                             int64_t L, float* logits, int* freqs,
                             bool portable) {
   if (n == 0) return;
-  const int C = (int)q_pad.size(0) - 4, H = (int)q_pad.size(1) - 8,
-            W = (int)q_pad.size(2) - 8;
+  const int64_t B = q_pad.size(0);
+  const int C = (int)q_pad.size(1) - 4, H = (int)q_pad.size(2) - 8,
+            W = (int)q_pad.size(3) - 8;
   const int kp = (int)((k + 7) / 8 * 8);
   auto kernel = portable ? pc_freqs_kernel<true> : pc_freqs_kernel<false>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(PC_THREADS), 0,
-                     at::cuda::getCurrentCUDAStream(),
-                     q_pad.data_ptr<float>(), C, H, W, pos,
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n, (unsigned)B), dim3(PC_THREADS),
+                     0, at::cuda::getCurrentCUDAStream(),
+                     q_pad.data_ptr<float>(), q_pad.stride(0), C, H, W, pos,
                      wts.data_ptr<float>(), (int)k, kp, (int)L, logits, freqs);
+}
+
+std::tuple<torch::Tensor, torch::Tensor> pc_freqs_batch(
+    torch::Tensor q_pad, torch::Tensor pos, torch::Tensor wts, int64_t k,
+    int64_t L, bool portable) {
+  pc_check(q_pad, pos, wts, k, L);
+  TORCH_CHECK(q_pad.dim() == 4, "pc_freqs_batch: q_pad must be 4-D");
+  const int64_t B = q_pad.size(0), n = pos.size(0);
+  auto logits = torch::empty({B, n, L}, q_pad.options());
+  auto freqs = torch::empty({B, n, L}, pos.options());
+  launch_pc_freqs(q_pad, pos.data_ptr<int>(), n, wts, k, L,
+                  logits.data_ptr<float>(), freqs.data_ptr<int>(), portable);
+  return {logits, freqs};
 }
 
 std::tuple<torch::Tensor, torch::Tensor> pc_freqs(torch::Tensor q_pad,
                                                   torch::Tensor pos,
                                                   torch::Tensor wts, int64_t k,
                                                   int64_t L, bool portable) {
-  pc_check(q_pad, pos, wts, k, L);
-  const int64_t n = pos.size(0);
-  auto logits = torch::empty({n, L}, q_pad.options());
-  auto freqs = torch::empty({n, L}, pos.options());
-  launch_pc_freqs(q_pad, pos.data_ptr<int>(), n, wts, k, L,
-                  logits.data_ptr<float>(), freqs.data_ptr<int>(), portable);
-  return {logits, freqs};
+  TORCH_CHECK(q_pad.dim() == 3, "pc_codec: q_pad must be fp32 (C+4, H+8, W+8)");
+  auto lf = pc_freqs_batch(q_pad.unsqueeze(0), pos, wts, k, L, portable);
+  return {std::get<0>(lf).squeeze(0), std::get<1>(lf).squeeze(0)};
 }
 
-// (8 + 3n + 16) bytes: little-endian payload length, then the payload.
-torch::Tensor rc_encode(torch::Tensor syms, torch::Tensor freqs) {
+// syms (B, n), freqs (B, n, L) -> (B, 8 + 3n + 16) bytes: row b holds the
+// little-endian payload length of image b, then its payload.
+torch::Tensor rc_encode_batch(torch::Tensor syms, torch::Tensor freqs) {
   CHECK_CUDA_CONTIG(syms);
   CHECK_CUDA_CONTIG(freqs);
-  TORCH_CHECK(syms.scalar_type() == torch::kInt32 && syms.dim() == 1,
-              "rc_encode: symbols must be int32 (n,)");
-  TORCH_CHECK(freqs.scalar_type() == torch::kInt32 && freqs.dim() == 2 &&
-                  freqs.size(0) == syms.size(0) && freqs.size(1) >= 1 &&
-                  freqs.size(1) <= PC_MAX_L,
-              "rc_encode: tables must be int32 (n, L<=16)");
-  const int64_t n = syms.size(0), L = freqs.size(1);
+  TORCH_CHECK(syms.scalar_type() == torch::kInt32 && syms.dim() == 2 &&
+                  syms.size(0) >= 1 && syms.size(0) <= PC_MAX_B,
+              "rc_encode: symbols must be int32 (B, n), B in [1, ", PC_MAX_B,
+              "]");
+  TORCH_CHECK(freqs.scalar_type() == torch::kInt32 && freqs.dim() == 3 &&
+                  freqs.size(0) == syms.size(0) &&
+                  freqs.size(1) == syms.size(1) && freqs.size(2) >= 1 &&
+                  freqs.size(2) <= PC_MAX_L,
+              "rc_encode: tables must be int32 (B, n, L<=16)");
+  const int64_t B = syms.size(0), n = syms.size(1), L = freqs.size(2);
   const int64_t cap = 3 * n + 16;
-  auto out = torch::empty({8 + cap}, syms.options().dtype(torch::kUInt8));
-  hipLaunchKernelGGL(rc_encode_kernel, dim3(1), dim3(RC_CHUNK), 0,
+  auto out = torch::empty({B, 8 + cap}, syms.options().dtype(torch::kUInt8));
+  hipLaunchKernelGGL(rc_encode_kernel, dim3((unsigned)B), dim3(RC_CHUNK), 0,
                      at::cuda::getCurrentCUDAStream(), syms.data_ptr<int>(),
                      freqs.data_ptr<int>(), n, (int)L,
                      out.data_ptr<uint8_t>(), (uint64_t)cap);
   return out;
+}
+
+// (8 + 3n + 16) bytes: little-endian payload length, then the payload.
+torch::Tensor rc_encode(torch::Tensor syms, torch::Tensor freqs) {
+  TORCH_CHECK(syms.dim() == 1, "rc_encode: symbols must be int32 (n,)");
+  TORCH_CHECK(freqs.dim() == 2 && freqs.size(0) == syms.size(0),
+              "rc_encode: tables must be int32 (n, L<=16)");
+  return rc_encode_batch(syms.unsqueeze(0), freqs.unsqueeze(0)).squeeze(0);
+}
+
+torch::Tensor pc_encode_batch(torch::Tensor q_pad, torch::Tensor pos,
+                              torch::Tensor syms, torch::Tensor wts,
+                              int64_t k, int64_t L, bool portable) {
+  TORCH_CHECK(q_pad.dim() == 4 && syms.dim() == 2 &&
+                  syms.size(0) == q_pad.size(0) &&
+                  syms.size(1) == pos.size(0),
+              "pc_encode_batch: one symbol per position and image");
+  auto lf = pc_freqs_batch(q_pad, pos, wts, k, L, portable);
+  return rc_encode_batch(syms, std::get<1>(lf));
 }
 
 torch::Tensor pc_encode(torch::Tensor q_pad, torch::Tensor pos,
@@ -419,13 +498,17 @@ torch::Tensor pc_encode(torch::Tensor q_pad, torch::Tensor pos,
   return rc_encode(syms, std::get<1>(lf));
 }
 
-static torch::Tensor decode_state(const torch::Tensor& data) {
-  auto state = torch::empty({(int64_t)(sizeof(rc::State) / 8)},
+// B decoder states, started by one launch. offs is null for a single image
+// (B = 1, the whole of data) and (B + 1) int64 on the device otherwise.
+static torch::Tensor decode_state(const torch::Tensor& data,
+                                  const int64_t* offs, int64_t B) {
+  auto state = torch::empty({B, (int64_t)(sizeof(rc::State) / 8)},
                             data.options().dtype(torch::kInt64));
-  hipLaunchKernelGGL(rc_decode_init_kernel, dim3(1), dim3(1), 0,
-                     at::cuda::getCurrentCUDAStream(),
+  hipLaunchKernelGGL(rc_decode_init_kernel, dim3((unsigned)((B + 63) / 64)),
+                     dim3(64), 0, at::cuda::getCurrentCUDAStream(),
                      reinterpret_cast<rc::State*>(state.data_ptr<int64_t>()),
-                     data.data_ptr<uint8_t>(), (uint64_t)data.numel());
+                     data.data_ptr<uint8_t>(), (uint64_t)data.numel(), offs,
+                     B);
   return state;
 }
 
@@ -441,25 +524,32 @@ torch::Tensor rc_decode(torch::Tensor data, torch::Tensor freqs) {
   const int64_t n = freqs.size(0), L = freqs.size(1);
   auto out = torch::zeros({n}, freqs.options().dtype(torch::kInt64));
   if (n == 0) return out;
-  auto state = decode_state(data);
+  auto state = decode_state(data, nullptr, 1);
   hipLaunchKernelGGL(rc_decode_wave_kernel, dim3(1), dim3(RC_CHUNK), 0,
                      at::cuda::getCurrentCUDAStream(),
                      reinterpret_cast<rc::State*>(state.data_ptr<int64_t>()),
                      data.data_ptr<uint8_t>(), (uint64_t)data.numel(),
-                     freqs.data_ptr<int>(), (const int*)nullptr, n, (int)L,
-                     (const float*)nullptr, (float*)nullptr, 0, 0, 0,
-                     out.data_ptr<int64_t>());
+                     (const int64_t*)nullptr, freqs.data_ptr<int>(),
+                     (const int*)nullptr, n, (int)L, (const float*)nullptr,
+                     (float*)nullptr, (int64_t)0, 0, 0, 0,
+                     out.data_ptr<int64_t>(), n);
   return out;
 }
 
-// Wavefront decode: wave i covers pos[offsets[i], offsets[i+1]). Two
-// launches per wave on the current stream, no host synchronisation. q_pad is
-// filled in place; returns the (C, H, W) int64 symbols.
-torch::Tensor pc_decode(torch::Tensor q_pad, torch::Tensor pos,
-                        std::vector<int64_t> offsets, torch::Tensor wts,
-                        int64_t k, int64_t L, torch::Tensor data,
-                        torch::Tensor centers, bool portable) {
+// Wavefront decode of B images: q_pad (B, C+4, H+8, W+8), wave i covers
+// pos[offsets[i], offsets[i+1]) in every image, image b's payload is
+// data[data_offs[b], data_offs[b+1]). One state init, then two launches per
+// wave on the current stream whatever B is, with no host synchronisation:
+// pc_freqs over (positions of the wave, images), rc_decode_wave with one
+// workgroup per image. q_pad is filled in place; returns the (B, C, H, W)
+// int64 symbols. B = 1 passes no offsets to the kernels and copies none.
+torch::Tensor pc_decode_batch(torch::Tensor q_pad, torch::Tensor pos,
+                              std::vector<int64_t> offsets, torch::Tensor wts,
+                              int64_t k, int64_t L, torch::Tensor data,
+                              std::vector<int64_t> data_offs,
+                              torch::Tensor centers, bool portable) {
   pc_check(q_pad, pos, wts, k, L);
+  TORCH_CHECK(q_pad.dim() == 4, "pc_decode_batch: q_pad must be 4-D");
   CHECK_CUDA_CONTIG(data);
   CHECK_CUDA_CONTIG(centers);
   TORCH_CHECK(data.scalar_type() == torch::kUInt8 && data.dim() == 1,
@@ -467,7 +557,11 @@ torch::Tensor pc_decode(torch::Tensor q_pad, torch::Tensor pos,
   TORCH_CHECK(centers.scalar_type() == torch::kFloat32 &&
                   centers.numel() == L,
               "pc_decode: centers must be fp32 (L,)");
-  const int64_t n = pos.size(0);
+  const int64_t B = q_pad.size(0), n = pos.size(0);
+  TORCH_CHECK((int64_t)data_offs.size() == B + 1 &&
+                  pcb::offsets_ok(data_offs.data(), B, data.numel()),
+              "pc_decode: payload offsets must be B+1 values running from 0 "
+              "to len(data) without decreasing");
   TORCH_CHECK(offsets.size() >= 1 && offsets.front() == 0 &&
                   offsets.back() == n,
               "pc_decode: wave offsets must run from 0 to n");
@@ -477,29 +571,48 @@ torch::Tensor pc_decode(torch::Tensor q_pad, torch::Tensor pos,
                 "pc_decode: wave offsets must not decrease");
     maxw = std::max(maxw, offsets[i] - offsets[i - 1]);
   }
-  const int C = (int)q_pad.size(0) - 4, H = (int)q_pad.size(1) - 8,
-            W = (int)q_pad.size(2) - 8;
-  auto out = torch::zeros({C, H, W}, pos.options().dtype(torch::kInt64));
+  const int C = (int)q_pad.size(1) - 4, H = (int)q_pad.size(2) - 8,
+            W = (int)q_pad.size(3) - 8;
+  auto out = torch::zeros({B, C, H, W}, pos.options().dtype(torch::kInt64));
   if (n == 0) return out;
-  auto logits = torch::empty({maxw, L}, q_pad.options());
-  auto freqs = torch::empty({maxw, L}, pos.options());
-  auto state = decode_state(data);
+  auto logits = torch::empty({B, maxw, L}, q_pad.options());
+  auto freqs = torch::empty({B, maxw, L}, pos.options());
+  torch::Tensor offs_dev;
+  const int64_t* offs = nullptr;
+  if (B > 1) {
+    offs_dev = torch::tensor(data_offs, torch::kInt64).to(data.device());
+    offs = offs_dev.data_ptr<int64_t>();
+  }
+  auto state = decode_state(data, offs, B);
   auto stream = at::cuda::getCurrentCUDAStream();
   const int* p = pos.data_ptr<int>();
   for (size_t i = 1; i < offsets.size(); ++i) {
     const int64_t o = offsets[i - 1], nw = offsets[i] - o;
     if (nw == 0) continue;
+    // the wave's tables are compact: (B, nw, L) at the head of the buffers
     launch_pc_freqs(q_pad, p + 3 * o, nw, wts, k, L, logits.data_ptr<float>(),
                     freqs.data_ptr<int>(), portable);
-    hipLaunchKernelGGL(rc_decode_wave_kernel, dim3(1), dim3(RC_CHUNK), 0,
-                       stream,
+    hipLaunchKernelGGL(rc_decode_wave_kernel, dim3((unsigned)B),
+                       dim3(RC_CHUNK), 0, stream,
                        reinterpret_cast<rc::State*>(state.data_ptr<int64_t>()),
-                       data.data_ptr<uint8_t>(), (uint64_t)data.numel(),
+                       data.data_ptr<uint8_t>(), (uint64_t)data.numel(), offs,
                        freqs.data_ptr<int>(), p + 3 * o, nw, (int)L,
-                       centers.data_ptr<float>(), q_pad.data_ptr<float>(), C,
-                       H, W, out.data_ptr<int64_t>());
+                       centers.data_ptr<float>(), q_pad.data_ptr<float>(),
+                       q_pad.stride(0), C, H, W, out.data_ptr<int64_t>(),
+                       (int64_t)C * H * W);
   }
   return out;
+}
+
+// The single image of pc_decode_batch: q_pad (C+4, H+8, W+8) -> (C, H, W).
+torch::Tensor pc_decode(torch::Tensor q_pad, torch::Tensor pos,
+                        std::vector<int64_t> offsets, torch::Tensor wts,
+                        int64_t k, int64_t L, torch::Tensor data,
+                        torch::Tensor centers, bool portable) {
+  TORCH_CHECK(q_pad.dim() == 3, "pc_codec: q_pad must be fp32 (C+4, H+8, W+8)");
+  return pc_decode_batch(q_pad.unsqueeze(0), pos, offsets, wts, k, L, data,
+                         {0, data.numel()}, centers, portable)
+      .squeeze(0);
 }
 
 // Host build of the same step functions (CPU tensors), for the tests.
@@ -515,24 +628,11 @@ torch::Tensor rc_encode_host(torch::Tensor syms, torch::Tensor freqs) {
   const int64_t n = syms.size(0), L = freqs.size(1);
   const int64_t cap = 3 * n + 16;
   auto out = torch::zeros({cap}, torch::kUInt8);
-  rc::State st;
-  rc::init(st);
-  const rc::ByteSink sink{out.data_ptr<uint8_t>(), (uint64_t)cap};
-  const int* sp = syms.data_ptr<int>();
-  const int* fp = freqs.data_ptr<int>();
-  for (int64_t i = 0; i < n; ++i) {
-    int s = sp[i] < 0 ? 0 : (sp[i] >= L ? (int)L - 1 : sp[i]);
-    uint32_t cum = 0, tot = 0;
-    for (int l = 0; l < L; ++l) {
-      if (l < s) cum += (uint32_t)fp[i * L + l];
-      tot += (uint32_t)fp[i * L + l];
-    }
-    rc::encode(st, sink, cum, (uint32_t)fp[i * L + s], tot);
-  }
-  rc::finish(st, sink);
-  TORCH_CHECK((int64_t)st.pos <= cap, "rc_encode_host: stream overran ", cap,
-              " bytes");
-  return out.slice(0, 0, (int64_t)st.pos).clone();
+  const int64_t len = (int64_t)pcb::encode_row(
+      syms.data_ptr<int>(), freqs.data_ptr<int>(), n, (int)L,
+      out.data_ptr<uint8_t>(), (uint64_t)cap);
+  TORCH_CHECK(len <= cap, "rc_encode_host: stream overran ", cap, " bytes");
+  return out.slice(0, 0, len).clone();
 }
 
 torch::Tensor rc_decode_host(torch::Tensor data, torch::Tensor freqs) {
@@ -640,17 +740,20 @@ static void pc_host_check(const torch::Tensor& q_pad, const torch::Tensor& pos,
               PC_MAX_K, "]");
   TORCH_CHECK(L >= 1 && L <= PC_MAX_L, "pc_codec: L must be in [1, ",
               PC_MAX_L, "]");
-  TORCH_CHECK(q_pad.scalar_type() == torch::kFloat32 && q_pad.dim() == 3 &&
-                  q_pad.size(0) > 4 && q_pad.size(1) > 8 && q_pad.size(2) > 8,
-              "pc_codec: q_pad must be fp32 (C+4, H+8, W+8)");
+  // (C+4, H+8, W+8), or (B, C+4, H+8, W+8) for the batch entry points
+  const int64_t d = q_pad.dim();
+  TORCH_CHECK(q_pad.scalar_type() == torch::kFloat32 && (d == 3 || d == 4) &&
+                  q_pad.size(d - 3) > 4 && q_pad.size(d - 2) > 8 &&
+                  q_pad.size(d - 1) > 8 && (d == 3 || q_pad.size(0) >= 1),
+              "pc_codec: q_pad must be fp32 ([B,] C+4, H+8, W+8)");
   TORCH_CHECK(pos.scalar_type() == torch::kInt32 && pos.dim() == 2 &&
                   pos.size(1) == 3,
               "pc_codec: positions must be int32 (n, 3)");
   TORCH_CHECK(wts.scalar_type() == torch::kFloat32 &&
                   wts.numel() == pc_packed_numel(k, L),
               "pc_codec: packed weights have the wrong size");
-  const int C = (int)q_pad.size(0) - 4, H = (int)q_pad.size(1) - 8,
-            W = (int)q_pad.size(2) - 8;
+  const int C = (int)q_pad.size(d - 3) - 4, H = (int)q_pad.size(d - 2) - 8,
+            W = (int)q_pad.size(d - 1) - 8;
   const int* p = pos.data_ptr<int>();
   for (int64_t i = 0; i < pos.size(0); ++i)
     TORCH_CHECK(p[3 * i] >= 0 && p[3 * i] < C && p[3 * i + 1] >= 0 &&
@@ -658,23 +761,44 @@ static void pc_host_check(const torch::Tensor& q_pad, const torch::Tensor& pos,
                 "pc_codec host: position ", i, " outside the volume");
 }
 
+// Tables (and logits) of positions [lo, hi) of a.pos in each of B images:
+// a describes image 0, image b lies q_stride floats further in q_pad and
+// n rows further in logits and freqs, which are (B, n, L). Images x
+// positions are spread over the threads together, so a narrow wave of a
+// large batch still fills them.
+static void pc_host_eval_batch(const PcHostArgs& a, int64_t B,
+                               int64_t q_stride, int64_t n, int64_t lo,
+                               int64_t hi) {
+  if (hi <= lo) return;
+  const bool hw = pc_host_cpu_has_fma() && !g_pc_host_force_libm.load();
+  const int L = a.wts.L;
+  host_parallel_for(0, B * (hi - lo), 1, [&](int64_t s, int64_t e) {
+    pcb::for_image_pieces(s, e, lo, hi, [&](int64_t b, int64_t plo,
+                                            int64_t phi) {
+      PcHostArgs ab = a;
+      ab.q_pad += b * q_stride;
+      if (ab.logits) ab.logits += b * n * L;
+      ab.freqs += b * n * L;
+      if (hw)
+        pc_host_range_hw(ab, plo, phi);
+      else
+        pc_host_range_libm(ab, plo, phi);
+    });
+  });
+}
+
 // Tables (and logits) of positions [lo, hi) of a.pos.
 static void pc_host_eval(const PcHostArgs& a, int64_t lo, int64_t hi) {
-  const bool hw = pc_host_cpu_has_fma() && !g_pc_host_force_libm.load();
-  host_parallel_for(lo, hi, 1, [&](int64_t b, int64_t e) {
-    if (hw)
-      pc_host_range_hw(a, b, e);
-    else
-      pc_host_range_libm(a, b, e);
-  });
+  pc_host_eval_batch(a, 1, 0, 0, lo, hi);
 }
 
 static PcHostArgs pc_host_args(const torch::Tensor& q_pad,
                                const torch::Tensor& pos,
                                const torch::Tensor& wts, int64_t k, int64_t L,
                                float* logits, int* freqs) {
-  return PcHostArgs{q_pad.data_ptr<float>(), (int)q_pad.size(1),
-                    (int)q_pad.size(2),      pos.data_ptr<int>(),
+  const int64_t d = q_pad.dim();
+  return PcHostArgs{q_pad.data_ptr<float>(), (int)q_pad.size(d - 2),
+                    (int)q_pad.size(d - 1),  pos.data_ptr<int>(),
                     pc::unpack(wts.data_ptr<float>(), (int)k, (int)L),
                     logits,                  freqs};
 }
@@ -683,6 +807,8 @@ std::tuple<torch::Tensor, torch::Tensor> pc_freqs_host(torch::Tensor q_pad,
                                                        torch::Tensor pos,
                                                        torch::Tensor wts,
                                                        int64_t k, int64_t L) {
+  TORCH_CHECK(q_pad.dim() == 3,
+              "pc_codec: q_pad must be fp32 (C+4, H+8, W+8)");
   pc_host_check(q_pad, pos, wts, k, L);
   const int64_t n = pos.size(0);
   auto logits = torch::empty({n, L}, q_pad.options());
@@ -697,6 +823,8 @@ std::tuple<torch::Tensor, torch::Tensor> pc_freqs_host(torch::Tensor q_pad,
 torch::Tensor pc_encode_host(torch::Tensor q_pad, torch::Tensor pos,
                              torch::Tensor syms, torch::Tensor wts, int64_t k,
                              int64_t L) {
+  TORCH_CHECK(q_pad.dim() == 3,
+              "pc_codec: q_pad must be fp32 (C+4, H+8, W+8)");
   pc_host_check(q_pad, pos, wts, k, L);
   TORCH_CHECK(!syms.is_cuda() && syms.is_contiguous() &&
                   syms.scalar_type() == torch::kInt32 && syms.dim() == 1 &&
@@ -710,12 +838,67 @@ torch::Tensor pc_encode_host(torch::Tensor q_pad, torch::Tensor pos,
   return rc_encode_host(syms, freqs);
 }
 
-// Wavefront decode on the host: wave i covers pos[offsets[i], offsets[i+1]).
-// q_pad is filled in place; returns the (C, H, W) int64 symbols.
-torch::Tensor pc_decode_host(torch::Tensor q_pad, torch::Tensor pos,
-                             std::vector<int64_t> offsets, torch::Tensor wts,
-                             int64_t k, int64_t L, torch::Tensor data,
-                             torch::Tensor centers) {
+// Batch forms of the three host functions: q_pad (B, C+4, H+8, W+8), one
+// position list. The bytes are those of B single-image calls.
+std::tuple<torch::Tensor, torch::Tensor> pc_freqs_batch_host(
+    torch::Tensor q_pad, torch::Tensor pos, torch::Tensor wts, int64_t k,
+    int64_t L) {
+  TORCH_CHECK(q_pad.dim() == 4, "pc_freqs_batch_host: q_pad must be 4-D");
+  pc_host_check(q_pad, pos, wts, k, L);
+  const int64_t B = q_pad.size(0), n = pos.size(0);
+  auto logits = torch::empty({B, n, L}, q_pad.options());
+  auto freqs = torch::empty({B, n, L}, pos.options());
+  pc_host_eval_batch(pc_host_args(q_pad, pos, wts, k, L,
+                                  logits.data_ptr<float>(),
+                                  freqs.data_ptr<int>()),
+                     B, q_pad.stride(0), n, 0, n);
+  return {logits, freqs};
+}
+
+// (B, 8 + 3n + 16) bytes, the layout of the device encoder: row b holds the
+// little-endian payload length of image b, then its payload.
+torch::Tensor pc_encode_batch_host(torch::Tensor q_pad, torch::Tensor pos,
+                                   torch::Tensor syms, torch::Tensor wts,
+                                   int64_t k, int64_t L) {
+  TORCH_CHECK(q_pad.dim() == 4, "pc_encode_batch_host: q_pad must be 4-D");
+  pc_host_check(q_pad, pos, wts, k, L);
+  const int64_t B = q_pad.size(0), n = pos.size(0);
+  TORCH_CHECK(!syms.is_cuda() && syms.is_contiguous() &&
+                  syms.scalar_type() == torch::kInt32 && syms.dim() == 2 &&
+                  syms.size(0) == B && syms.size(1) == n,
+              "pc_encode_batch_host: int32 (B, n) symbols, one per position "
+              "and image");
+  auto freqs = torch::empty({B, n, L}, pos.options());
+  pc_host_eval_batch(pc_host_args(q_pad, pos, wts, k, L, nullptr,
+                                  freqs.data_ptr<int>()),
+                     B, q_pad.stride(0), n, 0, n);
+  const int64_t cap = 3 * n + 16;
+  auto out = torch::zeros({B, 8 + cap}, torch::kUInt8);
+  const int* sp = syms.data_ptr<int>();
+  const int* fp = freqs.data_ptr<int>();
+  uint8_t* op = out.data_ptr<uint8_t>();
+  host_parallel_for(0, B, 1, [&](int64_t lo, int64_t hi) {
+    for (int64_t b = lo; b < hi; ++b) {
+      uint8_t* row = op + b * (8 + cap);
+      const uint64_t len = pcb::encode_row(sp + b * n, fp + b * n * L, n,
+                                           (int)L, row + 8, (uint64_t)cap);
+      for (int i = 0; i < 8; ++i) row[i] = (uint8_t)((len >> (8 * i)) & 0xFF);
+    }
+  });
+  return out;
+}
+
+// Wavefront decode of B images on the host: wave i covers
+// pos[offsets[i], offsets[i+1]) in every image, image b's payload is
+// data[data_offs[b], data_offs[b+1]). q_pad is filled in place; returns the
+// (B, C, H, W) int64 symbols.
+torch::Tensor pc_decode_batch_host(torch::Tensor q_pad, torch::Tensor pos,
+                                   std::vector<int64_t> offsets,
+                                   torch::Tensor wts, int64_t k, int64_t L,
+                                   torch::Tensor data,
+                                   std::vector<int64_t> data_offs,
+                                   torch::Tensor centers) {
+  TORCH_CHECK(q_pad.dim() == 4, "pc_decode_batch_host: q_pad must be 4-D");
   pc_host_check(q_pad, pos, wts, k, L);
   TORCH_CHECK(!data.is_cuda() && data.is_contiguous() &&
                   data.scalar_type() == torch::kUInt8 && data.dim() == 1,
@@ -724,42 +907,45 @@ torch::Tensor pc_decode_host(torch::Tensor q_pad, torch::Tensor pos,
                   centers.scalar_type() == torch::kFloat32 &&
                   centers.numel() == L,
               "pc_decode_host: centers must be CPU fp32 (L,)");
-  const int64_t n = pos.size(0);
+  const int64_t B = q_pad.size(0), n = pos.size(0);
+  TORCH_CHECK((int64_t)data_offs.size() == B + 1 &&
+                  pcb::offsets_ok(data_offs.data(), B, data.numel()),
+              "pc_decode_host: payload offsets must be B+1 values running "
+              "from 0 to len(data) without decreasing");
   TORCH_CHECK(offsets.size() >= 1 && offsets.front() == 0 &&
                   offsets.back() == n,
               "pc_decode_host: wave offsets must run from 0 to n");
   for (size_t i = 1; i < offsets.size(); ++i)
     TORCH_CHECK(offsets[i] >= offsets[i - 1],
                 "pc_decode_host: wave offsets must not decrease");
-  const int C = (int)q_pad.size(0) - 4, H = (int)q_pad.size(1) - 8,
-            W = (int)q_pad.size(2) - 8;
-  auto out = torch::zeros({C, H, W}, torch::kInt64);
+  const int C = (int)q_pad.size(1) - 4, H = (int)q_pad.size(2) - 8,
+            W = (int)q_pad.size(3) - 8;
+  auto out = torch::zeros({B, C, H, W}, torch::kInt64);
   if (n == 0) return out;
-  auto freqs = torch::empty({n, L}, pos.options());
+  auto freqs = torch::empty({B, n, L}, pos.options());
   const PcHostArgs a = pc_host_args(q_pad, pos, wts, k, L, nullptr,
                                     freqs.data_ptr<int>());
-  const rc::ByteSource src{data.data_ptr<uint8_t>(), (uint64_t)data.numel()};
-  rc::State st;
-  rc::decode_start(st, src);
-  const int* p = pos.data_ptr<int>();
-  const int* fp = freqs.data_ptr<int>();
-  const float* cen = centers.data_ptr<float>();
-  float* q = q_pad.data_ptr<float>();
-  int64_t* o = out.data_ptr<int64_t>();
-  uint32_t cum[rc::MAX_L + 1];
-  for (size_t wv = 1; wv < offsets.size(); ++wv) {
-    const int64_t lo = offsets[wv - 1], hi = offsets[wv];
-    if (hi == lo) continue;
-    pc_host_eval(a, lo, hi);
-    for (int64_t i = lo; i < hi; ++i) {
-      rc::cumulate(fp + i * L, (int)L, cum);
-      const int s = rc::decode_cum(st, src, cum, (int)L);
-      const int c = p[3 * i], h = p[3 * i + 1], w = p[3 * i + 2];
-      o[((int64_t)c * H + h) * W + w] = s;
-      q[((int64_t)(c + 4) * (H + 8) + (h + 4)) * (W + 8) + (w + 4)] = cen[s];
-    }
-  }
+  const int64_t q_stride = q_pad.stride(0);
+  const pcb::DecodeArgs d{B, n, (int)L, C, H, W, pos.data_ptr<int>(),
+                          freqs.data_ptr<int>(), data.data_ptr<uint8_t>(),
+                          data_offs.data(), centers.data_ptr<float>(),
+                          q_pad.data_ptr<float>(), out.data_ptr<int64_t>()};
+  pcb::decode_batch(d, offsets, [&](int64_t lo, int64_t hi) {
+    pc_host_eval_batch(a, B, q_stride, n, lo, hi);
+  });
   return out;
+}
+
+// The single image of pc_decode_batch_host: (C+4, H+8, W+8) -> (C, H, W).
+torch::Tensor pc_decode_host(torch::Tensor q_pad, torch::Tensor pos,
+                             std::vector<int64_t> offsets, torch::Tensor wts,
+                             int64_t k, int64_t L, torch::Tensor data,
+                             torch::Tensor centers) {
+  TORCH_CHECK(q_pad.dim() == 3,
+              "pc_codec: q_pad must be fp32 (C+4, H+8, W+8)");
+  return pc_decode_batch_host(q_pad.unsqueeze(0), pos, offsets, wts, k, L,
+                              data, {0, data.numel()}, centers)
+      .squeeze(0);
 }
 
 }  // namespace dsin

@@ -3,6 +3,7 @@
     python tools/bench_codec.py [--backend hip|torch|portable] [--device cpu]
                                 [--runs 5] [--warmup 1]
                                 [--shapes 32x8x12,32x40x120] [--zero-frac 0.5]
+                                [--batch 1,2,4,8,16]
 
 --device defaults to the GPU; --device cpu times the portable backend's host
 build (or the torch backend) and reports the thread count.
@@ -18,6 +19,18 @@ symbols.
 
 --backend torch calls encode_symbols / decode_symbols without the backend
 argument, so the tool also runs on a commit that predates it.
+
+--batch B1,B2,.. times the batched codec instead: for every shape and every
+B one JSON line with the time of ONE encode_symbols_batch /
+decode_symbols_batch call over B different symbol volumes ("batched") next
+to the time of B sequential encode_symbols / decode_symbols calls on the
+same volumes ("sequential"), taken alternately in the same process, their
+ratio (sequential median / batched median), the batched cost per image and
+the launch counts computed from the wave schedule (encode 2, decode
+1 + 2 * waves, whatever B is; nothing counts them at run time, the C++ wave
+loop issues exactly these and a kernel trace confirms it). Every
+decode, batched and sequential, is checked against the symbols, and the
+batched streams against the sequential ones.
 """
 
 import argparse
@@ -53,6 +66,56 @@ def stats(ts):
             "min": round(min(ts), 3), "max": round(max(ts), 3)}
 
 
+def bench_batch(args, dev, pc, centers, L, shape, B):
+    """One JSON line: a batched call against B sequential calls."""
+    from dsin_amd.coding import decode_symbols_batch, encode_symbols_batch
+    kw = {"backend": args.backend}
+    g = torch.Generator().manual_seed(1)
+    sym = torch.randint(0, L, (B,) + shape, generator=g)
+    sym[torch.rand(sym.shape, generator=g) < args.zero_frac] = 0
+    sym = sym.to(dev)
+    waves = len(_wave_order(*shape, pc.context_size() // 2))
+    t = {"eb": [], "es": [], "db": [], "ds": []}
+    for i in range(args.warmup + args.runs):
+        datas, eb = timed(lambda: encode_symbols_batch(pc, centers, sym,
+                                                       **kw), dev)
+        seq, es = timed(lambda: [encode_symbols(pc, centers, s, **kw)
+                                 for s in sym], dev)
+        if datas != seq:
+            sys.exit(f"bench_codec: batched streams differ at {shape}, B={B}")
+        out, db = timed(lambda: decode_symbols_batch(pc, centers, datas,
+                                                     shape, **kw), dev)
+        outs, ds = timed(lambda: [decode_symbols(pc, centers, d, shape, **kw)
+                                  for d in datas], dev)
+        if not (torch.equal(out, sym) and torch.equal(torch.stack(outs), sym)):
+            sys.exit(f"bench_codec: roundtrip failed at {shape}, B={B}")
+        if i >= args.warmup:
+            for k, v in zip(("eb", "es", "db", "ds"), (eb, es, db, ds)):
+                t[k].append(v)
+    med = {k: statistics.median(v) for k, v in t.items()}
+    out = {"backend": args.backend, "device": dev.type, "shape": list(shape),
+           "batch": B, "symbols_per_image": sym[0].numel(),
+           "zero_frac": args.zero_frac, "runs": args.runs,
+           "warmup": args.warmup, "waves": waves,
+           "stream_bytes": sum(len(d) for d in datas),
+           "encode_batched_ms": stats(t["eb"]),
+           "encode_sequential_ms": stats(t["es"]),
+           "encode_ratio": round(med["es"] / med["eb"], 3),
+           "encode_ms_per_image": round(med["eb"] / B, 3),
+           "decode_batched_ms": stats(t["db"]),
+           "decode_sequential_ms": stats(t["ds"]),
+           "decode_ratio": round(med["ds"] / med["db"], 3),
+           "decode_ms_per_image": round(med["db"] / B, 3)}
+    if dev.type != "cuda":
+        out["threads"] = torch.get_num_threads()
+    else:
+        # from the schedule, not counted: what the C++ loops issue
+        out["encode_launches_computed"] = {"batched": 2, "sequential": 2 * B}
+        out["decode_launches_computed"] = {"batched": 1 + 2 * waves,
+                                           "sequential": B * (1 + 2 * waves)}
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--backend", default="hip",
@@ -62,6 +125,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--shapes", default="32x8x12,32x40x120")
     ap.add_argument("--zero-frac", type=float, default=0.5)
+    ap.add_argument("--batch", default=None,
+                    help="comma-separated batch sizes: time one batched call "
+                         "against B sequential single-image calls")
     args = ap.parse_args()
     dev = torch.device(args.device)
     if dev.type == "cuda" and not torch.cuda.is_available():
@@ -79,6 +145,13 @@ def main():
 
     for spec in args.shapes.split(","):
         shape = tuple(int(s) for s in spec.split("x"))
+        if args.batch:
+            if args.backend == "torch":
+                sys.exit("bench_codec: --batch times the hip and portable "
+                         "backends (torch loops over the images)")
+            for B in (int(b) for b in args.batch.split(",")):
+                bench_batch(args, dev, pc, centers, L, shape, B)
+            continue
         g = torch.Generator().manual_seed(1)
         sym = torch.randint(0, L, shape, generator=g)
         sym[torch.rand(shape, generator=g) < args.zero_frac] = 0

@@ -3,6 +3,16 @@
     python tools/codec.py compress   [--backend portable] <checkpoint> <x.png> <out.dsin>
     python tools/codec.py decompress <checkpoint> <in.dsin> [--side y.png] <out.png>
 
+    python tools/codec.py compress-batch   [--backend portable] --out-dir DIR <checkpoint> <a.png> <b.png> ..
+    python tools/codec.py decompress-batch --out-dir DIR [--side ya.png --side yb.png ..] <checkpoint> <a.dsin> <b.dsin> ..
+
+compress-batch takes several images of one size and codes them in one
+compress_batch call (the entropy coder runs them as one batch on the GPU),
+writing DIR/<name>.dsin per image, each an ordinary single-image stream that
+decompress opens; decompress-batch takes several such streams of one size,
+decodes them in one decompress_batch call and writes DIR/<name>.png per
+stream (one --side per stream, in order, or none).
+
 <checkpoint> is a directory written by training (it holds model.pt). The
 model runs on the GPU when there is one (hip codec backend) and on the CPU
 otherwise (torch backend); a stream is decoded by the backend that wrote
@@ -25,7 +35,8 @@ import numpy as np
 import torch
 
 from dsin_amd import config as config_mod
-from dsin_amd.coding import compress, decompress
+from dsin_amd.coding import (compress, compress_batch, decompress,
+                             decompress_batch)
 from dsin_amd.coding.bitstream import parse_container
 from dsin_amd.data.png import read_png, write_png
 from dsin_amd.models import DSIN
@@ -71,6 +82,58 @@ def build_model(args, height: int, width: int, device) -> DSIN:
     return model.to(device).eval()
 
 
+def out_paths(out_dir: str, paths, ext: str):
+    names = [os.path.splitext(os.path.basename(p))[0] + ext for p in paths]
+    if len(set(names)) != len(names):
+        sys.exit("inputs of one batch need different file names")
+    os.makedirs(out_dir, exist_ok=True)
+    return [os.path.join(out_dir, n) for n in names]
+
+
+def run_batch(args, device, cast) -> None:
+    """All inputs in one compress_batch / decompress_batch call."""
+    if args.cmd == "compress-batch":
+        xs = [load_image(p, device) for p in args.paths]
+        if len(set(tuple(x.shape) for x in xs)) != 1:
+            sys.exit("images of one batch must have the same size")
+        outs = out_paths(args.out_dir, args.paths, ".dsin")
+        x = torch.stack(xs)
+        model = build_model(args, x.shape[2], x.shape[3], device)
+        with cast:
+            datas = compress_batch(model, x, backend=args.backend)
+        for path, data in zip(outs, datas):
+            with open(path, "wb") as f:
+                f.write(data)
+            bpp = 8.0 * len(data) / (x.shape[2] * x.shape[3])
+            print(f"{path}: {len(data)} bytes, {bpp:.4f} bpp")
+        return
+    datas = []
+    for p in args.paths:
+        with open(p, "rb") as f:
+            datas.append(f.read())
+    try:
+        _, (_, hb, wb), _, _, _ = parse_container(datas[0])
+    except ValueError as e:
+        sys.exit(f"{args.paths[0]}: {e}")
+    if args.side and len(args.side) != len(datas):
+        sys.exit(f"{len(datas)} streams need {len(datas)} --side images, "
+                 f"got {len(args.side)}")
+    outs = out_paths(args.out_dir, args.paths, ".png")
+    model = build_model(args, hb * 8, wb * 8, device)
+    y = (torch.stack([load_image(p, device) for p in args.side])
+         if args.side else None)
+    try:
+        with cast:
+            x_dec, x_si = decompress_batch(model, datas, y)
+    except ValueError as e:
+        sys.exit(f"{args.out_dir}: {e}")
+    res = x_si if x_si is not None else x_dec
+    for b, path in enumerate(outs):
+        save_image(path, res[b:b + 1])
+        print(f"{path}: {hb * 8}x{wb * 8}, "
+              f"{'x_with_si' if x_si is not None else 'x_dec'}")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--ae-config", default=os.path.join(
@@ -96,13 +159,32 @@ def main() -> None:
     d.add_argument("stream")
     d.add_argument("--side", default=None, help="side image y.png")
     d.add_argument("out")
+    cb = sub.add_parser("compress-batch",
+                        help="code several images of one size as one batch")
+    cb.add_argument("--backend", default=None,
+                    choices=["torch", "hip", "portable"])
+    cb.add_argument("--out-dir", required=True,
+                    help="receives one <name>.dsin per image")
+    cb.add_argument("checkpoint")
+    cb.add_argument("paths", nargs="+", metavar="image")
+    db = sub.add_parser("decompress-batch",
+                        help="decode several streams of one size as one batch")
+    db.add_argument("--out-dir", required=True,
+                    help="receives one <name>.png per stream")
+    db.add_argument("--side", action="append", default=None,
+                    help="side image y.png, once per stream and in their "
+                         "order, or not at all")
+    db.add_argument("checkpoint")
+    db.add_argument("paths", nargs="+", metavar="stream")
     args = ap.parse_args()
 
     device = torch.device(args.device or (
         "cuda:0" if torch.cuda.is_available() else "cpu"))
     cast = torch.autocast("cuda", dtype=torch.bfloat16, cache_enabled=False,
                           enabled=args.bf16 and device.type == "cuda")
-    if args.cmd == "compress":
+    if args.cmd.endswith("-batch"):
+        run_batch(args, device, cast)
+    elif args.cmd == "compress":
         x = load_image(args.image, device)
         model = build_model(args, x.shape[1], x.shape[2], device)
         with cast:
