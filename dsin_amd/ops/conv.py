@@ -433,18 +433,54 @@ def _out_size(h: int, k: int, s: int, p: int, d: int) -> int:
     return (h + 2 * p - (k - 1) * d - 1) // s + 1
 
 
+# field widths of the packed tables (conv_kernels.h): a signed 32-bit
+# kpack = ci<<20 | dh<<10 | dw and mpack = h<<16 | w
+_MAX_REACH = 1023
+_MAX_CHANNELS = 2047
+_MAX_ROW = 32767
+_MAX_COL = 65535
+
+
+def check_conv_geometry(what: str, Ci: int, Co: int, H: int, W: int,
+                        HO: int, WO: int, kh: int, kw: int, st: int,
+                        sv: int, dil: int) -> None:
+    """Refuse a geometry whose packed coordinate tables would overflow a
+    field, on both devices and before anything is launched: a carry into
+    the next field, or a set sign bit, decodes to an address outside the
+    tensor. Covers the forward tables (channels Ci, pixel coordinates
+    (HO-1)*st, (WO-1)*st), the backward-data tables (channels Co, pixel
+    coordinates (H-1)*sv, (W-1)*sv) and the phase tables, whose fields are
+    no larger than either."""
+    reach = (max(kh, kw) - 1) * dil
+    if reach > _MAX_REACH:
+        raise ValueError(f"{what}: tap reach (k-1)*dilation = {reach} "
+                         f"exceeds {_MAX_REACH}")
+    if max(Ci, Co) > _MAX_CHANNELS:
+        raise ValueError(f"{what}: {max(Ci, Co)} channels exceed "
+                         f"{_MAX_CHANNELS}")
+    row = max((HO - 1) * st, (H - 1) * sv)
+    col = max((WO - 1) * st, (W - 1) * sv)
+    if row > _MAX_ROW:
+        raise ValueError(f"{what}: row coordinate {row} exceeds {_MAX_ROW}")
+    if col > _MAX_COL:
+        raise ValueError(f"{what}: column coordinate {col} exceeds "
+                         f"{_MAX_COL}")
+
+
 def conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
            stride: int = 1, padding: int = 0, dilation: int = 1,
            act: int = 0) -> torch.Tensor:
     """Drop-in conv (NCHW). GPU: gather-GEMM MFMA kernel; CPU: torch oracle."""
-    if not x.is_cuda:
-        y = F.conv2d(x, w.to(x.dtype), bias.to(x.dtype) if bias is not None else None,
-                     stride=stride, padding=padding, dilation=dilation)
-        return _act(y, act)
     B, Ci, H, W = x.shape
     Co, _, kh, kw = w.shape
     HO = _out_size(H, kh, stride, padding, dilation)
     WO = _out_size(W, kw, stride, padding, dilation)
+    check_conv_geometry("conv2d", Ci, Co, H, W, HO, WO, kh, kw, stride, 1,
+                        dilation)
+    if not x.is_cuda:
+        y = F.conv2d(x, w.to(x.dtype), bias.to(x.dtype) if bias is not None else None,
+                     stride=stride, padding=padding, dilation=dilation)
+        return _act(y, act)
     if _COMPUTE == "fp8":
         return _GatherConvFP8Fn.apply(x, w.reshape(Co, Ci * kh * kw), bias,
                                       stride, dilation, kh, kw, HO, WO, act,
@@ -467,16 +503,18 @@ def conv_transpose2d(x: torch.Tensor, w: torch.Tensor,
                      padding: int = 0, output_padding: int = 0,
                      act: int = 0) -> torch.Tensor:
     """Transposed conv (w: (Ci, Co, kh, kw), the torch layout)."""
+    B, Ci, H, W = x.shape
+    _, Co, kh, kw = w.shape
+    HO = (H - 1) * stride - 2 * padding + kh + output_padding
+    WO = (W - 1) * stride - 2 * padding + kw + output_padding
+    check_conv_geometry("conv_transpose2d", Ci, Co, H, W, HO, WO, kh, kw, 1,
+                        stride, 1)
     if not x.is_cuda:
         y = F.conv_transpose2d(x, w.to(x.dtype),
                                bias.to(x.dtype) if bias is not None else None,
                                stride=stride, padding=padding,
                                output_padding=output_padding)
         return _act(y, act)
-    B, Ci, H, W = x.shape
-    _, Co, kh, kw = w.shape
-    HO = (H - 1) * stride - 2 * padding + kh + output_padding
-    WO = (W - 1) * stride - 2 * padding + kw + output_padding
     pl_h, pl_w = kh - 1 - padding, kw - 1 - padding
     w1 = w.flip(2, 3).permute(1, 0, 2, 3).reshape(Co, Ci * kh * kw)
     if _COMPUTE == "fp8":

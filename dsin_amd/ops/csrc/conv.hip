@@ -164,6 +164,8 @@ torch::Tensor conv_fwd(torch::Tensor xbuf, torch::Tensor wmat,
     if (!vm) return tm32 ? conv_fwd_kernel<32, 0, 0, 1>
                          : conv_fwd_kernel<64, 0, 0, 1>;
     // compile-time (stride, stuff) specialization for the virtual path
+    if (vsv > 2)  // backward-data of a stride >= 3 conv: run-time stuffing
+      return tm32 ? conv_fwd_kernel<32, 1, 0, 0> : conv_fwd_kernel<64, 1, 0, 0>;
     if (vsv == 2) {
       if (stride == 1)
         return tm32 ? conv_fwd_kernel<32, 1, 1, 2>

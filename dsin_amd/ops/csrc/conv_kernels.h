@@ -68,8 +68,12 @@ __global__ void conv_tables_kernel(int* __restrict__ mbase,
 // no pad_stuff kernel, no extra HBM round trip per conv.
 //   mpack[m] = (oh*stride) << 16 | (ow*stride)        (virtual-image coords)
 //   kpack[k] = ci << 20 | (r*dil) << 10 | (s*dil)
-// Field limits: ow*stride < 65536, ci < 4096, tap reach < 1024 — all DSIN
-// geometries (incl. 1024x2048 fp8 crops and siNet dil=128) fit.
+// Field limits: ow*stride < 65536, oh*stride < 32768 and ci < 2048 (the
+// entries are SIGNED ints decoded with arithmetic shifts: a set sign bit
+// gives a negative row or channel), tap reach < 1024 (a larger one carries
+// into the next field). ops/conv.py::check_conv_geometry refuses anything
+// else before a table is built; all DSIN geometries (incl. 1024x2048 fp8
+// crops and siNet dil=128) fit.
 __global__ void conv_tables_v2_kernel(int* __restrict__ mpack,
                                       int* __restrict__ kpack,
                                       int M, int K, int WO, int stride,
@@ -173,7 +177,9 @@ __device__ __forceinline__ void vstage8(const cvbf16* __restrict__ x,
 // and the padded-buffer HBM round trip per conv. VST/VSV are the
 // COMPILE-TIME conv stride / stuff stride for VM=1 (VST=0 = generic
 // per-element path for narrow outputs); runtime `stride`/`vsv` args are
-// used by the VM=0 path and must match VST/VSV when VM=1.
+// used by the VM=0 path and must match VST/VSV when VM=1. VSV=0 (with
+// VST=0 only) takes the stuff stride from the runtime `vsv`: the
+// backward-data gather of a conv whose stride is 3 or more.
 template <int TM, int VM, int VST, int VSV>
 __global__ __launch_bounds__(256)
 void conv_fwd_kernel(const cvbf16* __restrict__ xpad,   // see VM note above
@@ -286,6 +292,12 @@ void conv_fwd_kernel(const cvbf16* __restrict__ xpad,   // see VM note above
                  !(wv & 1) && (wv >> 1) < vW;
             a = ((long long)kci * vH + min(max(hv >> 1, 0), vH - 1)) * vW +
                 min(max(wv >> 1, 0), vW - 1);
+          } else if (VSV == 0) {  // run-time stuff stride vsv >= 3
+            const int hq = max(hv, 0) / vsv, wq = max(wv, 0) / vsv;
+            ok = hv >= 0 && wv >= 0 && hq * vsv == hv && wq * vsv == wv &&
+                 hq < vH && wq < vW;
+            a = ((long long)kci * vH + min(hq, vH - 1)) * vW +
+                min(wq, vW - 1);
           } else {
             ok = (unsigned)hv < (unsigned)vH && (unsigned)wv < (unsigned)vW;
             a = ((long long)kci * vH + min(max(hv, 0), vH - 1)) * vW +

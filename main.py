@@ -173,7 +173,8 @@ def main(argv=None):
             y_dec, y_syn, x_dec, x_with_si, bpp = model.reconstruct(x, y)
             x_rec = (x_with_si if x_with_si is not None and
                      float(x_with_si.abs().mean()) > 0 else x_dec)
-            x_rec_np = x_rec.clamp(0, 255).cpu().numpy()
+            # the GPU path returns bf16, which numpy does not take
+            x_rec_np = x_rec.float().clamp(0, 255).cpu().numpy()
             save_test_img(root_save_img, str(model_name), x_rec_np[0], i, float(bpp))
             loss_list_saver(x.cpu().numpy(), y.cpu().numpy(), x_rec_np,
                             y_syn.cpu().numpy() if y_syn is not None else None,
