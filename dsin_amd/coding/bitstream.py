@@ -59,7 +59,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from .entropy import (decode_symbols, decode_symbols_batch, encode_symbols,
+from .entropy import (decode_symbols, decode_symbols_batch,
                       encode_symbols_batch)
 
 MAGIC = b"DSIN"
@@ -133,25 +133,10 @@ def _as_batch(x: torch.Tensor, what: str) -> torch.Tensor:
 
 @torch.no_grad()
 def compress(model, x: torch.Tensor, backend: Optional[str] = None) -> bytes:
-    """Encode one image to a self-describing byte string. backend None is
-    the model's own (hip on a GPU, torch on the CPU); "portable" writes a
-    stream that any device decodes."""
-    if backend is not None and backend not in BACKEND_IDS:
-        raise ValueError(f"backend must be one of {tuple(BACKEND_IDS)}, got "
-                         f"{backend!r}")
-    from ..ops import conv as _conv
-    x = _as_batch(x, "x")
-    _conv.begin_step()
-    model.eval()
-    z = model.encoder(x)
-    symbols = z.symbols[0]
-    centers = model.encoder.quantizer.centers.detach()
-    if backend is None:
-        backend = model_backend(model)
-    payload = encode_symbols(model.probclass, centers, symbols,
-                             backend=backend)
-    return pack_container(backend, symbols.shape, centers.numel(),
-                          probclass_crc(model), payload)
+    """Encode one image to a self-describing byte string: compress_batch of
+    a batch of one. backend None is the model's own (hip on a GPU, torch on
+    the CPU); "portable" writes a stream that any device decodes."""
+    return compress_batch(model, _as_batch(x, "x"), backend)[0]
 
 
 def _check_header(model, bid: int, shape, L: int, crc: int) -> str:
@@ -179,13 +164,29 @@ def _check_header(model, bid: int, shape, L: int, crc: int) -> str:
     return backend
 
 
+def _reconstruct(model, symbols: torch.Tensor, y: Optional[torch.Tensor]
+                 ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Decoded symbols (B,C,Hb,Wb) and an optional side image (B,3,H,W) ->
+    (x_dec, x_with_si): the decoder on centers[symbols], then the
+    side-information search and the SI network."""
+    from .. import ops
+    centers = model.encoder.quantizer.centers.detach()
+    x_dec = model.decoder(centers.float()[symbols])
+    if y is None or model.ae_only:
+        return x_dec, None
+    y_dec = model.create_y_dec(y)
+    y_syn = model.sifinder(x_dec.float(), y.float(), y_dec.float())
+    cat = torch.cat([ops.kitti_normalize(x_dec),
+                     ops.kitti_normalize(y_syn.to(x_dec.dtype))], dim=1)
+    return x_dec, ops.kitti_denormalize(model.sinet(cat))
+
+
 @torch.no_grad()
 def decompress(model, data: bytes, y: Optional[torch.Tensor] = None
                ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """-> (x_dec, x_with_si). x_with_si is None without a side image y or
     for an AE-only model. Every header problem is a ValueError raised
     before any network or kernel runs."""
-    from .. import ops
     from ..ops import conv as _conv
     bid, shape, L, crc, payload = parse_container(data)
     backend = _check_header(model, bid, shape, L, crc)
@@ -196,15 +197,7 @@ def decompress(model, data: bytes, y: Optional[torch.Tensor] = None
     model.eval()
     symbols = decode_symbols(model.probclass, centers, payload, shape,
                              device=centers.device, backend=backend)
-    qbar = centers.float()[symbols].unsqueeze(0)
-    x_dec = model.decoder(qbar)
-    if y is None or model.ae_only:
-        return x_dec, None
-    y_dec = model.create_y_dec(y)
-    y_syn = model.sifinder(x_dec.float(), y.float(), y_dec.float())
-    cat = torch.cat([ops.kitti_normalize(x_dec),
-                     ops.kitti_normalize(y_syn.to(x_dec.dtype))], dim=1)
-    return x_dec, ops.kitti_denormalize(model.sinet(cat))
+    return _reconstruct(model, symbols[None], y)
 
 
 def _as_images(x: torch.Tensor, what: str) -> torch.Tensor:
@@ -246,7 +239,6 @@ def decompress_batch(model, datas: Sequence[bytes],
     containers; y is (B,3,H,W) when given. Every header problem, containers
     that differ in backend id, (C, Hb, Wb) or L, and a y of another batch
     size are ValueErrors raised before any network or kernel runs."""
-    from .. import ops
     from ..ops import conv as _conv
     datas = list(datas)
     if len(datas) < 1:
@@ -272,11 +264,4 @@ def decompress_batch(model, datas: Sequence[bytes],
     symbols = decode_symbols_batch(model.probclass, centers,
                                    [p[4] for p in parsed], shape,
                                    device=centers.device, backend=backend)
-    x_dec = model.decoder(centers.float()[symbols])
-    if y is None or model.ae_only:
-        return x_dec, None
-    y_dec = model.create_y_dec(y)
-    y_syn = model.sifinder(x_dec.float(), y.float(), y_dec.float())
-    cat = torch.cat([ops.kitti_normalize(x_dec),
-                     ops.kitti_normalize(y_syn.to(x_dec.dtype))], dim=1)
-    return x_dec, ops.kitti_denormalize(model.sinet(cat))
+    return _reconstruct(model, symbols, y)

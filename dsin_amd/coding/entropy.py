@@ -152,10 +152,11 @@ def _torch_backend_cache_reset(device: torch.device) -> None:
         _conv.begin_step()
 
 
-def _hip_setup(pc: ProbClass, centers: torch.Tensor, shape, device,
+def _hip_setup(pc: ProbClass, centers: torch.Tensor, B: int, shape, device,
                portable: bool = False):
-    """Checks + the pad-filled value buffer, wave-ordered positions and wave
-    offsets shared by the hip / portable encoder and decoder."""
+    """Checks + the pad-filled value buffers (B, C+4, H+8, W+8), wave-ordered
+    positions and wave offsets shared by the hip / portable encoder and
+    decoder."""
     from .. import ops
     ops.check_pc_shape(pc)
     name = "portable" if portable else "hip"
@@ -168,40 +169,19 @@ def _hip_setup(pc: ProbClass, centers: torch.Tensor, shape, device,
     waves = _wave_order(C, H, W, pad)
     pos = torch.from_numpy(np.concatenate(waves).astype(np.int32)).to(device)
     offsets = np.concatenate([[0], np.cumsum([len(w) for w in waves])])
-    q_pad = torch.full((C + pad, H + 2 * pad, W + 2 * pad),
+    q_pad = torch.full((B, C + pad, H + 2 * pad, W + 2 * pad),
                        float(_pad_value(pc, centers)),
                        dtype=torch.float32, device=device)
     return ops, pad, pos, offsets, q_pad
 
 
-def _encode_symbols_hip(pc, centers, symbols, portable=False) -> bytes:
-    dev = centers.device
-    ops, pad, pos, _, q_pad = _hip_setup(pc, centers, symbols.shape, dev,
-                                         portable)
-    sym = symbols.to(dev)
-    C, H, W = sym.shape
-    q_pad[pad:, pad:H + pad, pad:W + pad] = centers.float()[sym]
-    p = pos.long()
-    return ops.pc_encode(pc, q_pad, pos, sym[p[:, 0], p[:, 1], p[:, 2]],
-                         portable=portable)
-
-
-def _decode_symbols_hip(pc, centers, data, shape, device,
-                        portable=False) -> torch.Tensor:
-    ops, _, pos, offsets, q_pad = _hip_setup(pc, centers, shape, device,
-                                             portable)
-    return ops.pc_decode(pc, q_pad, pos, offsets, data, centers,
-                         portable=portable)
-
-
 def _encode_symbols_hip_batch(pc, centers, symbols,
                               portable=False) -> List[bytes]:
     dev = centers.device
-    ops, pad, pos, _, q1 = _hip_setup(pc, centers, symbols.shape[1:], dev,
-                                      portable)
+    B, C, H, W = symbols.shape
+    ops, pad, pos, _, q_pad = _hip_setup(pc, centers, B, (C, H, W), dev,
+                                         portable)
     sym = symbols.to(dev)
-    B, C, H, W = sym.shape
-    q_pad = q1.unsqueeze(0).repeat(B, 1, 1, 1)
     q_pad[:, pad:, pad:H + pad, pad:W + pad] = centers.float()[sym]
     p = pos.long()
     return ops.pc_encode_batch(pc, q_pad, pos,
@@ -211,9 +191,8 @@ def _encode_symbols_hip_batch(pc, centers, symbols,
 
 def _decode_symbols_hip_batch(pc, centers, datas, shape, device,
                               portable=False) -> torch.Tensor:
-    ops, _, pos, offsets, q1 = _hip_setup(pc, centers, shape, device,
-                                          portable)
-    q_pad = q1.unsqueeze(0).repeat(len(datas), 1, 1, 1)
+    ops, _, pos, offsets, q_pad = _hip_setup(pc, centers, len(datas), shape,
+                                             device, portable)
     return ops.pc_decode_batch(pc, q_pad, pos, offsets, datas, centers,
                                portable=portable)
 
@@ -273,7 +252,8 @@ def encode_symbols(pc: ProbClass, centers: torch.Tensor,
     """symbols: (C, H, W) int64 -> range-coded byte stream, wave order.
 
     backend="torch" (default): the per-wave torch path below, on any device.
-    backend="hip": the device-resident codec (ops.pc_encode; GPU only). The
+    backend="hip": the device-resident codec (a batch of one through
+    ops.pc_encode_batch; GPU only). The
     two backends do not decode each other's streams: their tables differ
     (fp32 kernels and a 65536-L table scale against the torch convs and a
     65536 scale).
@@ -292,8 +272,8 @@ def encode_symbols(pc: ProbClass, centers: torch.Tensor,
     """
     _check_backend(backend)
     if backend in ("hip", "portable"):
-        return _encode_symbols_hip(pc, centers, symbols,
-                                   portable=backend == "portable")
+        return _encode_symbols_hip_batch(pc, centers, symbols[None],
+                                         portable=backend == "portable")[0]
     sym = symbols.cpu().numpy()
     C, H, W = sym.shape
     pad = pc.context_size() // 2
@@ -331,15 +311,15 @@ def decode_symbols(pc: ProbClass, centers: torch.Tensor, data: bytes,
     inverse of encode_symbols with the same backend: one batched network
     call per skewed wave (O(25C + 5H + W) calls), then the wave's symbols
     are range-decoded sequentially against the batch's frequency tables.
-    backend="hip" keeps both steps on the GPU (ops.pc_decode);
+    backend="hip" keeps both steps on the GPU (ops.pc_decode_batch, B = 1);
     backend="portable" does the same on a GPU and runs the host build on
     the CPU, and decodes a portable stream written on either."""
     _check_backend(backend)
     C, H, W = shape
     device = torch.device(device or centers.device)
     if backend in ("hip", "portable"):
-        return _decode_symbols_hip(pc, centers, data, shape, device,
-                                   portable=backend == "portable")
+        return _decode_symbols_hip_batch(pc, centers, [data], shape, device,
+                                         portable=backend == "portable")[0]
     _torch_backend_cache_reset(device)
     pred = PredictionNetwork(pc, centers)
     pad = pc.context_size() // 2

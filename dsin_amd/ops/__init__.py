@@ -462,15 +462,6 @@ def pc_table_from_probs(p: torch.Tensor) -> torch.Tensor:
         torch.int32).clamp(min=1)
 
 
-def _pc_fn(name: str, q_pad: torch.Tensor):
-    """The extension entry for the device q_pad lives on (portable only on
-    the CPU); a missing extension is a RuntimeError on either."""
-    if q_pad.is_cuda:
-        return _require_ext(name)
-    return _require_ext(name + "_host",
-                        "for the portable codec on CPU tensors")
-
-
 def pc_host_fma_available() -> bool:
     """Whether this CPU runs the portable host path with hardware FMA."""
     return bool(_require_ext("pc_host_has_fma", "on the CPU")())
@@ -483,87 +474,19 @@ def pc_host_force_libm(on: bool) -> bool:
     return bool(_require_ext("pc_host_force_libm", "on the CPU")(bool(on)))
 
 
-def _pc_args(pc, q_pad: torch.Tensor, pos: torch.Tensor,
-             portable: bool = False):
-    k, L = check_pc_shape(pc)
-    if not q_pad.is_cuda and not portable:
-        raise ValueError("pc codec: the hip backend needs GPU tensors")
-    if q_pad.dim() != 3 or min(q_pad.shape[0] - 4, q_pad.shape[1] - 8,
-                               q_pad.shape[2] - 8) < 1:
-        raise ValueError(f"pc codec: q_pad must be (C+4, H+8, W+8), got "
-                         f"{tuple(q_pad.shape)}")
-    if pos.dim() != 2 or pos.shape[1] != 3:
-        raise ValueError("pc codec: positions must be (n, 3)")
-    return (k, L, q_pad.float().contiguous(),
-            pos.to(device=q_pad.device, dtype=torch.int32).contiguous())
-
-
-@torch.no_grad()
-def pc_freqs(pc, q_pad: torch.Tensor, pos: torch.Tensor,
-             packed: Optional[torch.Tensor] = None, portable: bool = False
-             ) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Context model at a list of positions of the padded value buffer:
-    (fp32 logits (n, L), int32 frequency tables (n, L)). GPU only, unless
-    portable=True, which also serves CPU tensors."""
-    k, L, q_pad, pos = _pc_args(pc, q_pad, pos, portable)
-    fn = _pc_fn("pc_freqs", q_pad)
-    if packed is None:
-        packed = pc_pack_weights(pc)
-    packed = packed.to(q_pad.device)
-    if not q_pad.is_cuda:
-        return fn(q_pad, pos, packed, k, L)
-    return fn(q_pad, pos, packed, k, L, portable)
-
-
-@torch.no_grad()
-def pc_encode(pc, q_pad: torch.Tensor, pos: torch.Tensor,
-              symbols: torch.Tensor, portable: bool = False) -> bytes:
-    """Range-code symbols (n,) at positions (n, 3) in the given order. GPU:
-    one pc_freqs launch, one rc_encode launch, one device-to-host copy.
-    CPU (portable only): the host build, same bytes."""
-    k, L, q_pad, pos = _pc_args(pc, q_pad, pos, portable)
-    fn = _pc_fn("pc_encode", q_pad)
-    syms = symbols.to(device=q_pad.device, dtype=torch.int32).contiguous()
-    packed = pc_pack_weights(pc).to(q_pad.device)
-    if not q_pad.is_cuda:
-        return fn(q_pad, pos, syms, packed, k, L).numpy().tobytes()
-    buf = fn(q_pad, pos, syms, packed, k, L, portable).cpu().numpy()
-    n = int.from_bytes(buf[:8].tobytes(), "little")
-    if n > buf.size - 8:
-        raise RuntimeError(f"pc_encode: stream of {n} bytes overran the "
-                           f"{buf.size - 8}-byte device buffer")
-    return buf[8:8 + n].tobytes()
-
-
-@torch.no_grad()
-def pc_decode(pc, q_pad: torch.Tensor, pos: torch.Tensor, offsets,
-              data: bytes, centers: torch.Tensor,
-              portable: bool = False) -> torch.Tensor:
-    """Wavefront decode: wave i is pos[offsets[i]:offsets[i+1]]. q_pad is
-    filled in place with centers[symbol]; returns (C, H, W) int64 symbols.
-    The wave loop runs in C++ (two launches per wave, no host sync)."""
-    k, L, q_pad_c, pos = _pc_args(pc, q_pad, pos, portable)
-    if q_pad_c.data_ptr() != q_pad.data_ptr():
-        raise ValueError("pc_decode: q_pad must be fp32 and contiguous")
-    fn = _pc_fn("pc_decode", q_pad)
-    raw = torch.frombuffer(bytearray(data) if len(data) else bytearray(1),
-                           dtype=torch.uint8)[:len(data)]
-    args = (q_pad, pos, [int(o) for o in offsets],
-            pc_pack_weights(pc).to(q_pad.device), k, L,
-            raw.to(q_pad.device).contiguous(),
-            centers.detach().to(q_pad.device).float().contiguous())
-    return fn(*args) if not q_pad.is_cuda else fn(*args, portable)
-
-
-# Batch forms: B images of one symbol-volume shape share the position list
-# and the wave schedule; q_pad is (B, C+4, H+8, W+8). The kernels are the
-# ones above with an image dimension (the calls above are their B = 1 case).
+# Below this file there is one form, the batch form: B images of one
+# symbol-volume shape share the position list and the wave schedule, q_pad is
+# (B, C+4, H+8, W+8), and the extension dispatches on the device of q_pad.
+# The single-image functions are B = 1 of the batch functions.
 
 PC_MAX_BATCH = 65535  # images per launch: the kernels' gridDim.y
 
 
-def _pc_batch_args(pc, q_pad: torch.Tensor, pos: torch.Tensor,
-                   portable: bool = False):
+def _pc_args(name: str, pc, q_pad: torch.Tensor, pos: torch.Tensor,
+             portable: bool = False):
+    """Checks every codec call makes, then the extension entry `name` (a
+    missing extension is a RuntimeError on either device); -> (entry, k, L,
+    fp32 contiguous q_pad, int32 positions on its device)."""
     k, L = check_pc_shape(pc)
     if not q_pad.is_cuda and not portable:
         raise ValueError("pc codec: the hip backend needs GPU tensors")
@@ -576,49 +499,32 @@ def _pc_batch_args(pc, q_pad: torch.Tensor, pos: torch.Tensor,
                          f"above the {PC_MAX_BATCH} one call codes; split it")
     if pos.dim() != 2 or pos.shape[1] != 3:
         raise ValueError("pc codec: positions must be (n, 3)")
-    return (k, L, q_pad.float().contiguous(),
+    fn = _require_ext(name, "on a GPU tensor" if q_pad.is_cuda else
+                      "for the portable codec on CPU tensors")
+    return (fn, k, L, q_pad.float().contiguous(),
             pos.to(device=q_pad.device, dtype=torch.int32).contiguous())
 
 
-@torch.no_grad()
-def pc_freqs_batch(pc, q_pad: torch.Tensor, pos: torch.Tensor,
-                   packed: Optional[torch.Tensor] = None,
-                   portable: bool = False
-                   ) -> Tuple[torch.Tensor, torch.Tensor]:
-    """pc_freqs over a batch: q_pad (B, C+4, H+8, W+8), positions (n, 3)
-    shared by all images -> (fp32 logits (B, n, L), int32 tables (B, n, L)),
-    one launch on the GPU. [b] equals pc_freqs of image b alone, bit for
-    bit."""
-    k, L, q_pad, pos = _pc_batch_args(pc, q_pad, pos, portable)
-    fn = _pc_fn("pc_freqs_batch", q_pad)
-    if packed is None:
-        packed = pc_pack_weights(pc)
-    packed = packed.to(q_pad.device)
-    if not q_pad.is_cuda:
-        return fn(q_pad, pos, packed, k, L)
-    return fn(q_pad, pos, packed, k, L, portable)
+def _pc_one(q_pad: torch.Tensor) -> torch.Tensor:
+    """The (C+4, H+8, W+8) buffer of a single-image call as a batch of one
+    (a view, so a decode still fills the caller's buffer)."""
+    if q_pad.dim() != 3:
+        raise ValueError(f"pc codec: q_pad must be (C+4, H+8, W+8), got "
+                         f"{tuple(q_pad.shape)}")
+    return q_pad[None]
 
 
-@torch.no_grad()
-def pc_encode_batch(pc, q_pad: torch.Tensor, pos: torch.Tensor,
-                    symbols: torch.Tensor, portable: bool = False
-                    ) -> List[bytes]:
-    """Range-code symbols (B, n) at positions (n, 3): one stream per image,
-    the bytes pc_encode gives for that image alone. GPU: one pc_freqs launch
-    over (positions, images), one rc_encode launch with a workgroup per
-    image, one device-to-host copy for the whole batch."""
-    k, L, q_pad, pos = _pc_batch_args(pc, q_pad, pos, portable)
-    if symbols.dim() != 2 or symbols.shape != (q_pad.shape[0], pos.shape[0]):
-        raise ValueError(f"pc_encode_batch: symbols must be (B, n) = "
-                         f"{(q_pad.shape[0], pos.shape[0])}, got "
-                         f"{tuple(symbols.shape)}")
-    fn = _pc_fn("pc_encode_batch", q_pad)
-    syms = symbols.to(device=q_pad.device, dtype=torch.int32).contiguous()
-    packed = pc_pack_weights(pc).to(q_pad.device)
-    if not q_pad.is_cuda:
-        buf = fn(q_pad, pos, syms, packed, k, L).numpy()
-    else:
-        buf = fn(q_pad, pos, syms, packed, k, L, portable).cpu().numpy()
+def _pc_bytes_tensor(data: bytes, device) -> torch.Tensor:
+    """bytes -> uint8 (len,) on device; b"" gives an empty tensor."""
+    raw = torch.frombuffer(bytearray(data) if len(data) else bytearray(1),
+                           dtype=torch.uint8)[:len(data)]
+    return raw.to(device).contiguous()
+
+
+def _pc_rows_to_bytes(rows: torch.Tensor) -> List[bytes]:
+    """(B, 8 + cap) uint8 rows, each a little-endian payload length and the
+    payload, -> the B payloads; a length above cap is an overrun."""
+    buf = rows.cpu().numpy()
     out = []
     for b in range(buf.shape[0]):
         n = int.from_bytes(buf[b, :8].tobytes(), "little")
@@ -631,32 +537,92 @@ def pc_encode_batch(pc, q_pad: torch.Tensor, pos: torch.Tensor,
 
 
 @torch.no_grad()
+def pc_freqs_batch(pc, q_pad: torch.Tensor, pos: torch.Tensor,
+                   packed: Optional[torch.Tensor] = None,
+                   portable: bool = False
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Context model at a list of positions of the padded value buffers:
+    q_pad (B, C+4, H+8, W+8), positions (n, 3) shared by all images ->
+    (fp32 logits (B, n, L), int32 frequency tables (B, n, L)), one launch on
+    the GPU. GPU only, unless portable=True, which also serves CPU tensors.
+    [b] does not depend on the other images, bit for bit."""
+    fn, k, L, q_pad, pos = _pc_args("pc_freqs", pc, q_pad, pos, portable)
+    if packed is None:
+        packed = pc_pack_weights(pc)
+    return fn(q_pad, pos, packed.to(q_pad.device), k, L, portable)
+
+
+@torch.no_grad()
+def pc_encode_batch(pc, q_pad: torch.Tensor, pos: torch.Tensor,
+                    symbols: torch.Tensor, portable: bool = False
+                    ) -> List[bytes]:
+    """Range-code symbols (B, n) at positions (n, 3) in the given order: one
+    stream per image, which does not depend on the other images. GPU: one
+    pc_freqs launch over (positions, images), one rc_encode launch with a
+    workgroup per image, one device-to-host copy for the whole batch. CPU
+    (portable only): the host build, same bytes."""
+    fn, k, L, q_pad, pos = _pc_args("pc_encode", pc, q_pad, pos, portable)
+    if symbols.dim() != 2 or symbols.shape != (q_pad.shape[0], pos.shape[0]):
+        raise ValueError(f"pc_encode_batch: symbols must be (B, n) = "
+                         f"{(q_pad.shape[0], pos.shape[0])}, got "
+                         f"{tuple(symbols.shape)}")
+    syms = symbols.to(device=q_pad.device, dtype=torch.int32).contiguous()
+    packed = pc_pack_weights(pc).to(q_pad.device)
+    return _pc_rows_to_bytes(fn(q_pad, pos, syms, packed, k, L, portable))
+
+
+@torch.no_grad()
 def pc_decode_batch(pc, q_pad: torch.Tensor, pos: torch.Tensor, offsets,
                     datas: Sequence[bytes], centers: torch.Tensor,
                     portable: bool = False) -> torch.Tensor:
     """Wavefront decode of B streams into q_pad (B, C+4, H+8, W+8), filled
-    in place; returns (B, C, H, W) int64 symbols. The payloads travel
-    concatenated with B+1 offsets, and each image's coder reads zeros past
-    the end of its own payload. One state init plus two launches per wave
-    for any B, issued from C++ without a host sync."""
-    k, L, q_pad_c, pos = _pc_batch_args(pc, q_pad, pos, portable)
+    in place with centers[symbol]; wave i is pos[offsets[i]:offsets[i+1]].
+    Returns (B, C, H, W) int64 symbols. The payloads travel concatenated
+    with B+1 offsets, and each image's coder reads zeros past the end of its
+    own payload. One state init plus two launches per wave for any B, issued
+    from C++ without a host sync."""
+    fn, k, L, q_pad_c, pos = _pc_args("pc_decode", pc, q_pad, pos, portable)
     if q_pad_c.data_ptr() != q_pad.data_ptr():
         raise ValueError("pc_decode_batch: q_pad must be fp32 and contiguous")
     if len(datas) != q_pad.shape[0]:
         raise ValueError(f"pc_decode_batch: {len(datas)} streams for a batch "
                          f"of {q_pad.shape[0]}")
-    fn = _pc_fn("pc_decode_batch", q_pad)
-    blob = b"".join(datas)
     data_offs = [0]
     for d in datas:
         data_offs.append(data_offs[-1] + len(d))
-    raw = torch.frombuffer(bytearray(blob) if len(blob) else bytearray(1),
-                           dtype=torch.uint8)[:len(blob)]
-    args = (q_pad, pos, [int(o) for o in offsets],
-            pc_pack_weights(pc).to(q_pad.device), k, L,
-            raw.to(q_pad.device).contiguous(), data_offs,
-            centers.detach().to(q_pad.device).float().contiguous())
-    return fn(*args) if not q_pad.is_cuda else fn(*args, portable)
+    return fn(q_pad, pos, [int(o) for o in offsets],
+              pc_pack_weights(pc).to(q_pad.device), k, L,
+              _pc_bytes_tensor(b"".join(datas), q_pad.device), data_offs,
+              centers.detach().to(q_pad.device).float().contiguous(),
+              portable)
+
+
+@torch.no_grad()
+def pc_freqs(pc, q_pad: torch.Tensor, pos: torch.Tensor,
+             packed: Optional[torch.Tensor] = None, portable: bool = False
+             ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """pc_freqs_batch of one image: q_pad (C+4, H+8, W+8) -> (fp32 logits
+    (n, L), int32 frequency tables (n, L))."""
+    lg, fr = pc_freqs_batch(pc, _pc_one(q_pad), pos, packed, portable)
+    return lg[0], fr[0]
+
+
+@torch.no_grad()
+def pc_encode(pc, q_pad: torch.Tensor, pos: torch.Tensor,
+              symbols: torch.Tensor, portable: bool = False) -> bytes:
+    """pc_encode_batch of one image: symbols (n,) -> its stream."""
+    return pc_encode_batch(pc, _pc_one(q_pad), pos, symbols[None],
+                           portable)[0]
+
+
+@torch.no_grad()
+def pc_decode(pc, q_pad: torch.Tensor, pos: torch.Tensor, offsets,
+              data: bytes, centers: torch.Tensor,
+              portable: bool = False) -> torch.Tensor:
+    """pc_decode_batch of one image: q_pad (C+4, H+8, W+8) is filled in
+    place; returns (C, H, W) int64 symbols."""
+    return pc_decode_batch(pc, _pc_one(q_pad), pos, offsets, [data], centers,
+                           portable)[0]
 
 
 # re-exports used across the package

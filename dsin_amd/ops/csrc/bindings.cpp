@@ -78,52 +78,18 @@ std::tuple<torch::Tensor, torch::Tensor> pc_freqs(torch::Tensor q_pad,
                                                   torch::Tensor pos,
                                                   torch::Tensor wts, int64_t k,
                                                   int64_t L, bool portable);
-torch::Tensor rc_encode(torch::Tensor syms, torch::Tensor freqs);
-torch::Tensor rc_decode(torch::Tensor data, torch::Tensor freqs);
 torch::Tensor pc_encode(torch::Tensor q_pad, torch::Tensor pos,
                         torch::Tensor syms, torch::Tensor wts, int64_t k,
                         int64_t L, bool portable);
 torch::Tensor pc_decode(torch::Tensor q_pad, torch::Tensor pos,
                         std::vector<int64_t> offsets, torch::Tensor wts,
                         int64_t k, int64_t L, torch::Tensor data,
-                        torch::Tensor centers, bool portable);
+                        std::vector<int64_t> data_offs, torch::Tensor centers,
+                        bool portable);
+torch::Tensor rc_encode(torch::Tensor syms, torch::Tensor freqs);
+torch::Tensor rc_decode(torch::Tensor data, torch::Tensor freqs);
 torch::Tensor rc_encode_host(torch::Tensor syms, torch::Tensor freqs);
 torch::Tensor rc_decode_host(torch::Tensor data, torch::Tensor freqs);
-std::tuple<torch::Tensor, torch::Tensor> pc_freqs_host(torch::Tensor q_pad,
-                                                       torch::Tensor pos,
-                                                       torch::Tensor wts,
-                                                       int64_t k, int64_t L);
-torch::Tensor pc_encode_host(torch::Tensor q_pad, torch::Tensor pos,
-                             torch::Tensor syms, torch::Tensor wts, int64_t k,
-                             int64_t L);
-torch::Tensor pc_decode_host(torch::Tensor q_pad, torch::Tensor pos,
-                             std::vector<int64_t> offsets, torch::Tensor wts,
-                             int64_t k, int64_t L, torch::Tensor data,
-                             torch::Tensor centers);
-std::tuple<torch::Tensor, torch::Tensor> pc_freqs_batch(
-    torch::Tensor q_pad, torch::Tensor pos, torch::Tensor wts, int64_t k,
-    int64_t L, bool portable);
-torch::Tensor rc_encode_batch(torch::Tensor syms, torch::Tensor freqs);
-torch::Tensor pc_encode_batch(torch::Tensor q_pad, torch::Tensor pos,
-                              torch::Tensor syms, torch::Tensor wts,
-                              int64_t k, int64_t L, bool portable);
-torch::Tensor pc_decode_batch(torch::Tensor q_pad, torch::Tensor pos,
-                              std::vector<int64_t> offsets, torch::Tensor wts,
-                              int64_t k, int64_t L, torch::Tensor data,
-                              std::vector<int64_t> data_offs,
-                              torch::Tensor centers, bool portable);
-std::tuple<torch::Tensor, torch::Tensor> pc_freqs_batch_host(
-    torch::Tensor q_pad, torch::Tensor pos, torch::Tensor wts, int64_t k,
-    int64_t L);
-torch::Tensor pc_encode_batch_host(torch::Tensor q_pad, torch::Tensor pos,
-                                   torch::Tensor syms, torch::Tensor wts,
-                                   int64_t k, int64_t L);
-torch::Tensor pc_decode_batch_host(torch::Tensor q_pad, torch::Tensor pos,
-                                   std::vector<int64_t> offsets,
-                                   torch::Tensor wts, int64_t k, int64_t L,
-                                   torch::Tensor data,
-                                   std::vector<int64_t> data_offs,
-                                   torch::Tensor centers);
 bool pc_host_force_libm(bool on);
 std::string pc_host_path();
 bool pc_host_has_fma();
@@ -169,50 +135,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "one-scale SSIM/CS analytic gradient");
   m.def("down2_fwd", &dsin::down2_fwd, "MS-SSIM dyadic downsample");
   m.def("down2_bwd", &dsin::down2_bwd, "MS-SSIM dyadic downsample adjoint");
+  // Entropy codec: q_pad is (B, C+4, H+8, W+8) and picks the device (HIP
+  // kernels on a GPU tensor, the portable host build on a CPU tensor).
   m.def("pc_freqs", &dsin::pc_freqs,
-        "probclass context model per position: (logits, frequency tables)",
+        "probclass context model per position: (B, n, L) logits and tables",
         py::arg("q_pad"), py::arg("pos"), py::arg("wts"), py::arg("k"),
         py::arg("L"), py::arg("portable") = false);
-  m.def("rc_encode", &dsin::rc_encode, "device range encoder");
-  m.def("rc_decode", &dsin::rc_decode, "device range decoder, given tables");
-  m.def("pc_encode", &dsin::pc_encode, "context model + range encoder",
+  m.def("pc_encode", &dsin::pc_encode,
+        "context model + range encoder: (B, 8 + 3n + 16) length-prefixed rows",
         py::arg("q_pad"), py::arg("pos"), py::arg("syms"), py::arg("wts"),
         py::arg("k"), py::arg("L"), py::arg("portable") = false);
-  m.def("pc_decode", &dsin::pc_decode, "wavefront context-model decoder",
+  m.def("pc_decode", &dsin::pc_decode,
+        "wavefront context-model decoder, concatenated payloads",
         py::arg("q_pad"), py::arg("pos"), py::arg("offsets"), py::arg("wts"),
-        py::arg("k"), py::arg("L"), py::arg("data"), py::arg("centers"),
-        py::arg("portable") = false);
+        py::arg("k"), py::arg("L"), py::arg("data"), py::arg("data_offs"),
+        py::arg("centers"), py::arg("portable") = false);
+  m.def("rc_encode", &dsin::rc_encode,
+        "device range encoder, one workgroup per image");
+  m.def("rc_decode", &dsin::rc_decode, "device range decoder, given tables");
   m.def("rc_encode_host", &dsin::rc_encode_host,
         "host build of the range-encoder step functions");
   m.def("rc_decode_host", &dsin::rc_decode_host,
         "host build of the range-decoder step functions");
-  m.def("pc_freqs_host", &dsin::pc_freqs_host,
-        "portable context model on CPU tensors: (logits, frequency tables)");
-  m.def("pc_encode_host", &dsin::pc_encode_host,
-        "portable context model + range encoder on CPU tensors");
-  m.def("pc_decode_host", &dsin::pc_decode_host,
-        "portable wavefront decoder on CPU tensors");
-  m.def("pc_freqs_batch", &dsin::pc_freqs_batch,
-        "pc_freqs over (B, C+4, H+8, W+8): (B, n, L) logits and tables",
-        py::arg("q_pad"), py::arg("pos"), py::arg("wts"), py::arg("k"),
-        py::arg("L"), py::arg("portable") = false);
-  m.def("rc_encode_batch", &dsin::rc_encode_batch,
-        "device range encoder, one workgroup per image");
-  m.def("pc_encode_batch", &dsin::pc_encode_batch,
-        "context model + range encoder over a batch of images",
-        py::arg("q_pad"), py::arg("pos"), py::arg("syms"), py::arg("wts"),
-        py::arg("k"), py::arg("L"), py::arg("portable") = false);
-  m.def("pc_decode_batch", &dsin::pc_decode_batch,
-        "wavefront decoder over a batch of images, concatenated payloads",
-        py::arg("q_pad"), py::arg("pos"), py::arg("offsets"), py::arg("wts"),
-        py::arg("k"), py::arg("L"), py::arg("data"), py::arg("data_offs"),
-        py::arg("centers"), py::arg("portable") = false);
-  m.def("pc_freqs_batch_host", &dsin::pc_freqs_batch_host,
-        "portable context model over a batch of CPU images");
-  m.def("pc_encode_batch_host", &dsin::pc_encode_batch_host,
-        "portable context model + range encoder over a batch of CPU images");
-  m.def("pc_decode_batch_host", &dsin::pc_decode_batch_host,
-        "portable wavefront decoder over a batch of CPU images");
   m.def("pc_host_force_libm", &dsin::pc_host_force_libm,
         "force the library-fmaf host path; returns the previous setting");
   m.def("pc_host_path", &dsin::pc_host_path,

@@ -2,9 +2,12 @@
 // position (pc_freqs) and a range coder that never leaves the GPU
 // (rc_encode / rc_decode_wave).
 //
-// Every kernel takes a batch of B images of one symbol-volume shape: the
-// value buffer is (B, C+4, H+8, W+8), the position list is shared, and the
-// single-image entry points are the B = 1 case of the same kernels.
+// Every kernel and every entry point takes a batch of B images of one
+// symbol-volume shape: the value buffer is (B, C+4, H+8, W+8), the position
+// list is shared, outputs are (B, ...). One image is B = 1, which the Python
+// layer decides. The three context-model entry points (pc_freqs, pc_encode,
+// pc_decode) dispatch on the device of q_pad: kernels for a GPU tensor, the
+// host build of the portable backend for a CPU tensor.
 //
 // pc_freqs: one workgroup per (queried position (c, h, w), image); the image
 // is blockIdx.y. The position's 5x9x9 causal context is read from the padded
@@ -36,7 +39,7 @@
 //
 // PORTABLE instantiation (codec backend id 2): the same conv chain with the
 // ReLU and the table epilogue of pc_model.h, which a host build reproduces
-// bit for bit (pc_freqs_host / pc_encode_host / pc_decode_host below).
+// bit for bit (the CPU branch of the entry points below).
 
 #include <atomic>
 #include <functional>
@@ -52,16 +55,10 @@
 
 namespace dsin {
 
-constexpr int PC_MAX_K = 32;
-constexpr int PC_MAX_L = rc::MAX_L;
+// The model's sizes are pc_model.h's (pc::MAX_K, pc::NT_FIRST, pc::S0, ...).
 constexpr int PC_MAX_B = 65535;  // images per launch: gridDim.y
 constexpr int PC_THREADS = 256;
-constexpr int PC_NT_FIRST = 13;
-constexpr int PC_NT_OTHER = 14;
-constexpr int PC_S0 = 4 * 7 * 7;   // conv0 output sites
-constexpr int PC_S1 = 3 * 5 * 5;   // res_conv1 output sites
-constexpr int PC_S2 = 2 * 3 * 3;   // res_conv2 output sites
-constexpr int PC_SIN = 5 * 9 * 9;  // context sites
+static_assert(pc::MAX_L == rc::MAX_L, "model and coder disagree on MAX_L");
 
 template <int CG> struct WVec;
 template <> struct WVec<8> {
@@ -120,7 +117,7 @@ __device__ __forceinline__ void pc_layer(const float* in, float* out,
     for (int j = 0; j < CG; ++j) {
       float r = acc[j];
       if (SKIP)
-        r += skip[(co0 + j) * PC_S0 + (d + 2) * 49 + (h + 2) * 7 + (x + 2)];
+        r += skip[(co0 + j) * pc::S0 + (d + 2) * 49 + (h + 2) * 7 + (x + 2)];
       if (RELU) r = PORTABLE ? pc::relu(r) : fmaxf(r, 0.f);
       out[(co0 + j) * So + p] = r;
     }
@@ -133,13 +130,13 @@ pc_freqs_kernel(const float* __restrict__ q_pad, int64_t q_stride, int C,
                 int H, int W, const int* __restrict__ pos,
                 const float* __restrict__ wts, int k, int kp, int L,
                 float* __restrict__ logits, int* __restrict__ freqs) {
-  __shared__ float s_in[PC_SIN + 3];
-  __shared__ float s_a0[PC_MAX_K * PC_S0];
-  __shared__ float s_a1[PC_MAX_K * PC_S1];
-  __shared__ float s_a2[PC_MAX_K * PC_S2];
-  __shared__ float s_part[PC_NT_OTHER * PC_MAX_L];
-  __shared__ float s_lg[PC_MAX_L];
-  __shared__ uint32_t s_u[PC_MAX_L];  // PORTABLE table weights
+  __shared__ float s_in[pc::SIN + 3];
+  __shared__ float s_a0[pc::MAX_K * pc::S0];
+  __shared__ float s_a1[pc::MAX_K * pc::S1];
+  __shared__ float s_a2[pc::MAX_K * pc::S2];
+  __shared__ float s_part[pc::NT_OTHER * pc::MAX_L];
+  __shared__ float s_lg[pc::MAX_L];
+  __shared__ uint32_t s_u[pc::MAX_L];  // PORTABLE table weights
 
   // position blockIdx.x of image blockIdx.y; outputs are (B, n, L)
   const int64_t ip = blockIdx.x;
@@ -155,42 +152,42 @@ pc_freqs_kernel(const float* __restrict__ q_pad, int64_t q_stride, int C,
     return;
   }
   const int Hp = H + 8, Wp = W + 8;
-  for (int i = tid; i < PC_SIN; i += PC_THREADS) {
+  for (int i = tid; i < pc::SIN; i += PC_THREADS) {
     const int d = i / 81, r = i - d * 81, y = r / 9, x = r - y * 9;
     s_in[i] = q_pad[((int64_t)(c + d) * Hp + (h + y)) * Wp + (w + x)];
   }
   const float* w0 = wts;
-  const float* b0 = w0 + PC_NT_FIRST * kp;
+  const float* b0 = w0 + pc::NT_FIRST * kp;
   const float* w1 = b0 + kp;
-  const float* b1 = w1 + (size_t)PC_NT_OTHER * k * kp;
+  const float* b1 = w1 + (size_t)pc::NT_OTHER * k * kp;
   const float* w2 = b1 + kp;
-  const float* b2 = w2 + (size_t)PC_NT_OTHER * k * kp;
+  const float* b2 = w2 + (size_t)pc::NT_OTHER * k * kp;
   const float* w3 = b2 + kp;
-  const float* b3 = w3 + (size_t)PC_NT_OTHER * k * L;
+  const float* b3 = w3 + (size_t)pc::NT_OTHER * k * L;
   __syncthreads();
-  pc_layer<PORTABLE, 8, PC_NT_FIRST, 5, 9, 9, true, false>(
+  pc_layer<PORTABLE, 8, pc::NT_FIRST, 5, 9, 9, true, false>(
       s_in, s_a0, w0, b0, 1, kp, nullptr);
   __syncthreads();
-  pc_layer<PORTABLE, 8, PC_NT_OTHER, 4, 7, 7, true, false>(
+  pc_layer<PORTABLE, 8, pc::NT_OTHER, 4, 7, 7, true, false>(
       s_a0, s_a1, w1, b1, k, kp, nullptr);
   __syncthreads();
-  pc_layer<PORTABLE, 2, PC_NT_OTHER, 3, 5, 5, false, true>(
+  pc_layer<PORTABLE, 2, pc::NT_OTHER, 3, 5, 5, false, true>(
       s_a1, s_a2, w2, b2, k, kp, s_a0);
   __syncthreads();
   // conv2: one output site; tap t of the 2x3x3 input is site t. Thread
   // (t, l) sums over ci, then thread l adds the 14 partials in tap order.
-  if (tid < PC_NT_OTHER * L) {
+  if (tid < pc::NT_OTHER * L) {
     const int t = tid / L, l = tid - t * L;
     float acc = 0.f;
     const float* wt = w3 + (size_t)t * k * L + l;
     for (int ci = 0; ci < k; ++ci)
-      acc = fmaf(s_a2[ci * PC_S2 + t], wt[ci * L], acc);
-    s_part[t * PC_MAX_L + l] = acc;
+      acc = fmaf(s_a2[ci * pc::S2 + t], wt[ci * L], acc);
+    s_part[t * pc::MAX_L + l] = acc;
   }
   __syncthreads();
   if (tid < L) {
     float acc = b3[tid];
-    for (int t = 0; t < PC_NT_OTHER; ++t) acc += s_part[t * PC_MAX_L + tid];
+    for (int t = 0; t < pc::NT_OTHER; ++t) acc += s_part[t * pc::MAX_L + tid];
     s_lg[tid] = acc;
   }
   __syncthreads();
@@ -373,292 +370,6 @@ rc_decode_wave_kernel(rc::State* state, const uint8_t* __restrict__ data_all,
 }
 
 // ---------------------------------------------------------------------------
-// Host wrappers
-// ---------------------------------------------------------------------------
-
-static int64_t pc_packed_numel(int64_t k, int64_t L) {
-  const int64_t kp = (k + 7) / 8 * 8;
-  return PC_NT_FIRST * kp + kp + 2 * (PC_NT_OTHER * k * kp + kp) +
-         PC_NT_OTHER * k * L + L;
-}
-
-static void pc_check(const torch::Tensor& q_pad, const torch::Tensor& pos,
-                     const torch::Tensor& wts, int64_t k, int64_t L) {
-  CHECK_CUDA_CONTIG(q_pad);
-  CHECK_CUDA_CONTIG(pos);
-  CHECK_CUDA_CONTIG(wts);
-  TORCH_CHECK(k >= 1 && k <= PC_MAX_K, "pc_codec: k must be in [1, ",
-              PC_MAX_K, "]");
-  TORCH_CHECK(L >= 1 && L <= PC_MAX_L, "pc_codec: L must be in [1, ",
-              PC_MAX_L, "]");
-  // (C+4, H+8, W+8), or (B, C+4, H+8, W+8) for the batch entry points
-  const int64_t d = q_pad.dim();
-  TORCH_CHECK(q_pad.scalar_type() == torch::kFloat32 && (d == 3 || d == 4) &&
-                  q_pad.size(d - 3) > 4 && q_pad.size(d - 2) > 8 &&
-                  q_pad.size(d - 1) > 8,
-              "pc_codec: q_pad must be fp32 ([B,] C+4, H+8, W+8)");
-  TORCH_CHECK(d == 3 || (q_pad.size(0) >= 1 && q_pad.size(0) <= PC_MAX_B),
-              "pc_codec: batch size must be in [1, ", PC_MAX_B, "]");
-  TORCH_CHECK(pos.scalar_type() == torch::kInt32 && pos.dim() == 2 &&
-                  pos.size(1) == 3,
-              "pc_codec: positions must be int32 (n, 3)");
-  TORCH_CHECK(wts.scalar_type() == torch::kFloat32 &&
-                  wts.numel() == pc_packed_numel(k, L),
-              "pc_codec: packed weights have the wrong size");
-}
-
-// q_pad is (B, C+4, H+8, W+8); logits and freqs are (B, n, L).
-static void launch_pc_freqs(const torch::Tensor& q_pad, const int* pos,
-                            int64_t n, const torch::Tensor& wts, int64_t k,
-                            int64_t L, float* logits, int* freqs,
-                            bool portable) {
-  if (n == 0) return;
-  const int64_t B = q_pad.size(0);
-  const int C = (int)q_pad.size(1) - 4, H = (int)q_pad.size(2) - 8,
-            W = (int)q_pad.size(3) - 8;
-  const int kp = (int)((k + 7) / 8 * 8);
-  auto kernel = portable ? pc_freqs_kernel<true> : pc_freqs_kernel<false>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)n, (unsigned)B), dim3(PC_THREADS),
-                     0, at::cuda::getCurrentCUDAStream(),
-                     q_pad.data_ptr<float>(), q_pad.stride(0), C, H, W, pos,
-                     wts.data_ptr<float>(), (int)k, kp, (int)L, logits, freqs);
-}
-
-std::tuple<torch::Tensor, torch::Tensor> pc_freqs_batch(
-    torch::Tensor q_pad, torch::Tensor pos, torch::Tensor wts, int64_t k,
-    int64_t L, bool portable) {
-  pc_check(q_pad, pos, wts, k, L);
-  TORCH_CHECK(q_pad.dim() == 4, "pc_freqs_batch: q_pad must be 4-D");
-  const int64_t B = q_pad.size(0), n = pos.size(0);
-  auto logits = torch::empty({B, n, L}, q_pad.options());
-  auto freqs = torch::empty({B, n, L}, pos.options());
-  launch_pc_freqs(q_pad, pos.data_ptr<int>(), n, wts, k, L,
-                  logits.data_ptr<float>(), freqs.data_ptr<int>(), portable);
-  return {logits, freqs};
-}
-
-std::tuple<torch::Tensor, torch::Tensor> pc_freqs(torch::Tensor q_pad,
-                                                  torch::Tensor pos,
-                                                  torch::Tensor wts, int64_t k,
-                                                  int64_t L, bool portable) {
-  TORCH_CHECK(q_pad.dim() == 3, "pc_codec: q_pad must be fp32 (C+4, H+8, W+8)");
-  auto lf = pc_freqs_batch(q_pad.unsqueeze(0), pos, wts, k, L, portable);
-  return {std::get<0>(lf).squeeze(0), std::get<1>(lf).squeeze(0)};
-}
-
-// syms (B, n), freqs (B, n, L) -> (B, 8 + 3n + 16) bytes: row b holds the
-// little-endian payload length of image b, then its payload.
-torch::Tensor rc_encode_batch(torch::Tensor syms, torch::Tensor freqs) {
-  CHECK_CUDA_CONTIG(syms);
-  CHECK_CUDA_CONTIG(freqs);
-  TORCH_CHECK(syms.scalar_type() == torch::kInt32 && syms.dim() == 2 &&
-                  syms.size(0) >= 1 && syms.size(0) <= PC_MAX_B,
-              "rc_encode: symbols must be int32 (B, n), B in [1, ", PC_MAX_B,
-              "]");
-  TORCH_CHECK(freqs.scalar_type() == torch::kInt32 && freqs.dim() == 3 &&
-                  freqs.size(0) == syms.size(0) &&
-                  freqs.size(1) == syms.size(1) && freqs.size(2) >= 1 &&
-                  freqs.size(2) <= PC_MAX_L,
-              "rc_encode: tables must be int32 (B, n, L<=16)");
-  const int64_t B = syms.size(0), n = syms.size(1), L = freqs.size(2);
-  const int64_t cap = 3 * n + 16;
-  auto out = torch::empty({B, 8 + cap}, syms.options().dtype(torch::kUInt8));
-  hipLaunchKernelGGL(rc_encode_kernel, dim3((unsigned)B), dim3(RC_CHUNK), 0,
-                     at::cuda::getCurrentCUDAStream(), syms.data_ptr<int>(),
-                     freqs.data_ptr<int>(), n, (int)L,
-                     out.data_ptr<uint8_t>(), (uint64_t)cap);
-  return out;
-}
-
-// (8 + 3n + 16) bytes: little-endian payload length, then the payload.
-torch::Tensor rc_encode(torch::Tensor syms, torch::Tensor freqs) {
-  TORCH_CHECK(syms.dim() == 1, "rc_encode: symbols must be int32 (n,)");
-  TORCH_CHECK(freqs.dim() == 2 && freqs.size(0) == syms.size(0),
-              "rc_encode: tables must be int32 (n, L<=16)");
-  return rc_encode_batch(syms.unsqueeze(0), freqs.unsqueeze(0)).squeeze(0);
-}
-
-torch::Tensor pc_encode_batch(torch::Tensor q_pad, torch::Tensor pos,
-                              torch::Tensor syms, torch::Tensor wts,
-                              int64_t k, int64_t L, bool portable) {
-  TORCH_CHECK(q_pad.dim() == 4 && syms.dim() == 2 &&
-                  syms.size(0) == q_pad.size(0) &&
-                  syms.size(1) == pos.size(0),
-              "pc_encode_batch: one symbol per position and image");
-  auto lf = pc_freqs_batch(q_pad, pos, wts, k, L, portable);
-  return rc_encode_batch(syms, std::get<1>(lf));
-}
-
-torch::Tensor pc_encode(torch::Tensor q_pad, torch::Tensor pos,
-                        torch::Tensor syms, torch::Tensor wts, int64_t k,
-                        int64_t L, bool portable) {
-  TORCH_CHECK(syms.dim() == 1 && syms.size(0) == pos.size(0),
-              "pc_encode: one symbol per position");
-  auto lf = pc_freqs(q_pad, pos, wts, k, L, portable);
-  return rc_encode(syms, std::get<1>(lf));
-}
-
-// B decoder states, started by one launch. offs is null for a single image
-// (B = 1, the whole of data) and (B + 1) int64 on the device otherwise.
-static torch::Tensor decode_state(const torch::Tensor& data,
-                                  const int64_t* offs, int64_t B) {
-  auto state = torch::empty({B, (int64_t)(sizeof(rc::State) / 8)},
-                            data.options().dtype(torch::kInt64));
-  hipLaunchKernelGGL(rc_decode_init_kernel, dim3((unsigned)((B + 63) / 64)),
-                     dim3(64), 0, at::cuda::getCurrentCUDAStream(),
-                     reinterpret_cast<rc::State*>(state.data_ptr<int64_t>()),
-                     data.data_ptr<uint8_t>(), (uint64_t)data.numel(), offs,
-                     B);
-  return state;
-}
-
-// Decode n symbols against given tables (n, L) in one launch.
-torch::Tensor rc_decode(torch::Tensor data, torch::Tensor freqs) {
-  CHECK_CUDA_CONTIG(data);
-  CHECK_CUDA_CONTIG(freqs);
-  TORCH_CHECK(data.scalar_type() == torch::kUInt8 && data.dim() == 1,
-              "rc_decode: data must be uint8 (len,)");
-  TORCH_CHECK(freqs.scalar_type() == torch::kInt32 && freqs.dim() == 2 &&
-                  freqs.size(1) >= 1 && freqs.size(1) <= PC_MAX_L,
-              "rc_decode: tables must be int32 (n, L<=16)");
-  const int64_t n = freqs.size(0), L = freqs.size(1);
-  auto out = torch::zeros({n}, freqs.options().dtype(torch::kInt64));
-  if (n == 0) return out;
-  auto state = decode_state(data, nullptr, 1);
-  hipLaunchKernelGGL(rc_decode_wave_kernel, dim3(1), dim3(RC_CHUNK), 0,
-                     at::cuda::getCurrentCUDAStream(),
-                     reinterpret_cast<rc::State*>(state.data_ptr<int64_t>()),
-                     data.data_ptr<uint8_t>(), (uint64_t)data.numel(),
-                     (const int64_t*)nullptr, freqs.data_ptr<int>(),
-                     (const int*)nullptr, n, (int)L, (const float*)nullptr,
-                     (float*)nullptr, (int64_t)0, 0, 0, 0,
-                     out.data_ptr<int64_t>(), n);
-  return out;
-}
-
-// Wavefront decode of B images: q_pad (B, C+4, H+8, W+8), wave i covers
-// pos[offsets[i], offsets[i+1]) in every image, image b's payload is
-// data[data_offs[b], data_offs[b+1]). One state init, then two launches per
-// wave on the current stream whatever B is, with no host synchronisation:
-// pc_freqs over (positions of the wave, images), rc_decode_wave with one
-// workgroup per image. q_pad is filled in place; returns the (B, C, H, W)
-// int64 symbols. B = 1 passes no offsets to the kernels and copies none.
-torch::Tensor pc_decode_batch(torch::Tensor q_pad, torch::Tensor pos,
-                              std::vector<int64_t> offsets, torch::Tensor wts,
-                              int64_t k, int64_t L, torch::Tensor data,
-                              std::vector<int64_t> data_offs,
-                              torch::Tensor centers, bool portable) {
-  pc_check(q_pad, pos, wts, k, L);
-  TORCH_CHECK(q_pad.dim() == 4, "pc_decode_batch: q_pad must be 4-D");
-  CHECK_CUDA_CONTIG(data);
-  CHECK_CUDA_CONTIG(centers);
-  TORCH_CHECK(data.scalar_type() == torch::kUInt8 && data.dim() == 1,
-              "pc_decode: data must be uint8 (len,)");
-  TORCH_CHECK(centers.scalar_type() == torch::kFloat32 &&
-                  centers.numel() == L,
-              "pc_decode: centers must be fp32 (L,)");
-  const int64_t B = q_pad.size(0), n = pos.size(0);
-  TORCH_CHECK((int64_t)data_offs.size() == B + 1 &&
-                  pcb::offsets_ok(data_offs.data(), B, data.numel()),
-              "pc_decode: payload offsets must be B+1 values running from 0 "
-              "to len(data) without decreasing");
-  TORCH_CHECK(offsets.size() >= 1 && offsets.front() == 0 &&
-                  offsets.back() == n,
-              "pc_decode: wave offsets must run from 0 to n");
-  int64_t maxw = 0;
-  for (size_t i = 1; i < offsets.size(); ++i) {
-    TORCH_CHECK(offsets[i] >= offsets[i - 1],
-                "pc_decode: wave offsets must not decrease");
-    maxw = std::max(maxw, offsets[i] - offsets[i - 1]);
-  }
-  const int C = (int)q_pad.size(1) - 4, H = (int)q_pad.size(2) - 8,
-            W = (int)q_pad.size(3) - 8;
-  auto out = torch::zeros({B, C, H, W}, pos.options().dtype(torch::kInt64));
-  if (n == 0) return out;
-  auto logits = torch::empty({B, maxw, L}, q_pad.options());
-  auto freqs = torch::empty({B, maxw, L}, pos.options());
-  torch::Tensor offs_dev;
-  const int64_t* offs = nullptr;
-  if (B > 1) {
-    offs_dev = torch::tensor(data_offs, torch::kInt64).to(data.device());
-    offs = offs_dev.data_ptr<int64_t>();
-  }
-  auto state = decode_state(data, offs, B);
-  auto stream = at::cuda::getCurrentCUDAStream();
-  const int* p = pos.data_ptr<int>();
-  for (size_t i = 1; i < offsets.size(); ++i) {
-    const int64_t o = offsets[i - 1], nw = offsets[i] - o;
-    if (nw == 0) continue;
-    // the wave's tables are compact: (B, nw, L) at the head of the buffers
-    launch_pc_freqs(q_pad, p + 3 * o, nw, wts, k, L, logits.data_ptr<float>(),
-                    freqs.data_ptr<int>(), portable);
-    hipLaunchKernelGGL(rc_decode_wave_kernel, dim3((unsigned)B),
-                       dim3(RC_CHUNK), 0, stream,
-                       reinterpret_cast<rc::State*>(state.data_ptr<int64_t>()),
-                       data.data_ptr<uint8_t>(), (uint64_t)data.numel(), offs,
-                       freqs.data_ptr<int>(), p + 3 * o, nw, (int)L,
-                       centers.data_ptr<float>(), q_pad.data_ptr<float>(),
-                       q_pad.stride(0), C, H, W, out.data_ptr<int64_t>(),
-                       (int64_t)C * H * W);
-  }
-  return out;
-}
-
-// The single image of pc_decode_batch: q_pad (C+4, H+8, W+8) -> (C, H, W).
-torch::Tensor pc_decode(torch::Tensor q_pad, torch::Tensor pos,
-                        std::vector<int64_t> offsets, torch::Tensor wts,
-                        int64_t k, int64_t L, torch::Tensor data,
-                        torch::Tensor centers, bool portable) {
-  TORCH_CHECK(q_pad.dim() == 3, "pc_codec: q_pad must be fp32 (C+4, H+8, W+8)");
-  return pc_decode_batch(q_pad.unsqueeze(0), pos, offsets, wts, k, L, data,
-                         {0, data.numel()}, centers, portable)
-      .squeeze(0);
-}
-
-// Host build of the same step functions (CPU tensors), for the tests.
-torch::Tensor rc_encode_host(torch::Tensor syms, torch::Tensor freqs) {
-  TORCH_CHECK(!syms.is_cuda() && !freqs.is_cuda() && syms.is_contiguous() &&
-                  freqs.is_contiguous(),
-              "rc_encode_host: CPU contiguous tensors");
-  TORCH_CHECK(syms.scalar_type() == torch::kInt32 && syms.dim() == 1 &&
-                  freqs.scalar_type() == torch::kInt32 && freqs.dim() == 2 &&
-                  freqs.size(0) == syms.size(0) && freqs.size(1) >= 1 &&
-                  freqs.size(1) <= PC_MAX_L,
-              "rc_encode_host: int32 (n,) symbols and (n, L<=16) tables");
-  const int64_t n = syms.size(0), L = freqs.size(1);
-  const int64_t cap = 3 * n + 16;
-  auto out = torch::zeros({cap}, torch::kUInt8);
-  const int64_t len = (int64_t)pcb::encode_row(
-      syms.data_ptr<int>(), freqs.data_ptr<int>(), n, (int)L,
-      out.data_ptr<uint8_t>(), (uint64_t)cap);
-  TORCH_CHECK(len <= cap, "rc_encode_host: stream overran ", cap, " bytes");
-  return out.slice(0, 0, len).clone();
-}
-
-torch::Tensor rc_decode_host(torch::Tensor data, torch::Tensor freqs) {
-  TORCH_CHECK(!data.is_cuda() && !freqs.is_cuda() && data.is_contiguous() &&
-                  freqs.is_contiguous(),
-              "rc_decode_host: CPU contiguous tensors");
-  TORCH_CHECK(data.scalar_type() == torch::kUInt8 && data.dim() == 1 &&
-                  freqs.scalar_type() == torch::kInt32 && freqs.dim() == 2 &&
-                  freqs.size(1) >= 1 && freqs.size(1) <= PC_MAX_L,
-              "rc_decode_host: uint8 data and int32 (n, L<=16) tables");
-  const int64_t n = freqs.size(0), L = freqs.size(1);
-  auto out = torch::zeros({n}, torch::kInt32);
-  const rc::ByteSource src{data.data_ptr<uint8_t>(), (uint64_t)data.numel()};
-  rc::State st;
-  rc::decode_start(st, src);
-  const int* fp = freqs.data_ptr<int>();
-  int* op = out.data_ptr<int>();
-  uint32_t cum[rc::MAX_L + 1];
-  for (int64_t i = 0; i < n; ++i) {
-    rc::cumulate(fp + i * L, (int)L, cum);
-    op[i] = rc::decode_cum(st, src, cum, (int)L);
-  }
-  return out;
-}
-
-// ---------------------------------------------------------------------------
 // Host build of the portable backend (CPU tensors): pc_model.h per position,
 // positions of a wave spread over at::parallel_for, the coder step functions
 // of rc_coder.h. A position's logits and table depend on nothing but q_pad
@@ -730,45 +441,13 @@ std::string pc_host_path() {
 
 bool pc_host_has_fma() { return pc_host_cpu_has_fma(); }
 
-static void pc_host_check(const torch::Tensor& q_pad, const torch::Tensor& pos,
-                          const torch::Tensor& wts, int64_t k, int64_t L) {
-  TORCH_CHECK(!q_pad.is_cuda() && !pos.is_cuda() && !wts.is_cuda() &&
-                  q_pad.is_contiguous() && pos.is_contiguous() &&
-                  wts.is_contiguous(),
-              "pc_codec host: CPU contiguous tensors");
-  TORCH_CHECK(k >= 1 && k <= PC_MAX_K, "pc_codec: k must be in [1, ",
-              PC_MAX_K, "]");
-  TORCH_CHECK(L >= 1 && L <= PC_MAX_L, "pc_codec: L must be in [1, ",
-              PC_MAX_L, "]");
-  // (C+4, H+8, W+8), or (B, C+4, H+8, W+8) for the batch entry points
-  const int64_t d = q_pad.dim();
-  TORCH_CHECK(q_pad.scalar_type() == torch::kFloat32 && (d == 3 || d == 4) &&
-                  q_pad.size(d - 3) > 4 && q_pad.size(d - 2) > 8 &&
-                  q_pad.size(d - 1) > 8 && (d == 3 || q_pad.size(0) >= 1),
-              "pc_codec: q_pad must be fp32 ([B,] C+4, H+8, W+8)");
-  TORCH_CHECK(pos.scalar_type() == torch::kInt32 && pos.dim() == 2 &&
-                  pos.size(1) == 3,
-              "pc_codec: positions must be int32 (n, 3)");
-  TORCH_CHECK(wts.scalar_type() == torch::kFloat32 &&
-                  wts.numel() == pc_packed_numel(k, L),
-              "pc_codec: packed weights have the wrong size");
-  const int C = (int)q_pad.size(d - 3) - 4, H = (int)q_pad.size(d - 2) - 8,
-            W = (int)q_pad.size(d - 1) - 8;
-  const int* p = pos.data_ptr<int>();
-  for (int64_t i = 0; i < pos.size(0); ++i)
-    TORCH_CHECK(p[3 * i] >= 0 && p[3 * i] < C && p[3 * i + 1] >= 0 &&
-                    p[3 * i + 1] < H && p[3 * i + 2] >= 0 && p[3 * i + 2] < W,
-                "pc_codec host: position ", i, " outside the volume");
-}
-
 // Tables (and logits) of positions [lo, hi) of a.pos in each of B images:
 // a describes image 0, image b lies q_stride floats further in q_pad and
 // n rows further in logits and freqs, which are (B, n, L). Images x
 // positions are spread over the threads together, so a narrow wave of a
 // large batch still fills them.
-static void pc_host_eval_batch(const PcHostArgs& a, int64_t B,
-                               int64_t q_stride, int64_t n, int64_t lo,
-                               int64_t hi) {
+static void pc_host_eval(const PcHostArgs& a, int64_t B, int64_t q_stride,
+                         int64_t n, int64_t lo, int64_t hi) {
   if (hi <= lo) return;
   const bool hw = pc_host_cpu_has_fma() && !g_pc_host_force_libm.load();
   const int L = a.wts.L;
@@ -787,91 +466,150 @@ static void pc_host_eval_batch(const PcHostArgs& a, int64_t B,
   });
 }
 
-// Tables (and logits) of positions [lo, hi) of a.pos.
-static void pc_host_eval(const PcHostArgs& a, int64_t lo, int64_t hi) {
-  pc_host_eval_batch(a, 1, 0, 0, lo, hi);
-}
-
 static PcHostArgs pc_host_args(const torch::Tensor& q_pad,
                                const torch::Tensor& pos,
                                const torch::Tensor& wts, int64_t k, int64_t L,
                                float* logits, int* freqs) {
-  const int64_t d = q_pad.dim();
-  return PcHostArgs{q_pad.data_ptr<float>(), (int)q_pad.size(d - 2),
-                    (int)q_pad.size(d - 1),  pos.data_ptr<int>(),
+  return PcHostArgs{q_pad.data_ptr<float>(), (int)q_pad.size(2),
+                    (int)q_pad.size(3),      pos.data_ptr<int>(),
                     pc::unpack(wts.data_ptr<float>(), (int)k, (int)L),
                     logits,                  freqs};
 }
 
-std::tuple<torch::Tensor, torch::Tensor> pc_freqs_host(torch::Tensor q_pad,
-                                                       torch::Tensor pos,
-                                                       torch::Tensor wts,
-                                                       int64_t k, int64_t L) {
-  TORCH_CHECK(q_pad.dim() == 3,
-              "pc_codec: q_pad must be fp32 (C+4, H+8, W+8)");
-  pc_host_check(q_pad, pos, wts, k, L);
-  const int64_t n = pos.size(0);
-  auto logits = torch::empty({n, L}, q_pad.options());
-  auto freqs = torch::empty({n, L}, pos.options());
-  pc_host_eval(pc_host_args(q_pad, pos, wts, k, L, logits.data_ptr<float>(),
-                            freqs.data_ptr<int>()),
-               0, n);
-  return {logits, freqs};
+// ---------------------------------------------------------------------------
+// Entry points. q_pad is (B, C+4, H+8, W+8) and decides the device: the
+// kernels above for a GPU tensor, the host build for a CPU tensor (portable
+// only). Every other tensor lives where q_pad does.
+// ---------------------------------------------------------------------------
+
+static void pc_check_tensor(const torch::Tensor& t, const char* what,
+                            bool on_gpu) {
+  TORCH_CHECK(t.is_cuda() == on_gpu && t.is_contiguous(), "pc_codec: ", what,
+              " must be contiguous on the ", on_gpu ? "GPU" : "CPU",
+              ", where q_pad is");
 }
 
-// The payload bytes (no length prefix).
-torch::Tensor pc_encode_host(torch::Tensor q_pad, torch::Tensor pos,
-                             torch::Tensor syms, torch::Tensor wts, int64_t k,
-                             int64_t L) {
-  TORCH_CHECK(q_pad.dim() == 3,
-              "pc_codec: q_pad must be fp32 (C+4, H+8, W+8)");
-  pc_host_check(q_pad, pos, wts, k, L);
-  TORCH_CHECK(!syms.is_cuda() && syms.is_contiguous() &&
-                  syms.scalar_type() == torch::kInt32 && syms.dim() == 1 &&
-                  syms.size(0) == pos.size(0),
-              "pc_encode_host: int32 (n,) symbols, one per position");
-  const int64_t n = pos.size(0);
-  auto freqs = torch::empty({n, L}, pos.options());
-  pc_host_eval(pc_host_args(q_pad, pos, wts, k, L, nullptr,
-                            freqs.data_ptr<int>()),
-               0, n);
-  return rc_encode_host(syms, freqs);
+static void pc_check(const torch::Tensor& q_pad, const torch::Tensor& pos,
+                     const torch::Tensor& wts, int64_t k, int64_t L,
+                     bool on_gpu, bool portable) {
+  TORCH_CHECK(on_gpu || portable,
+              "pc_codec: CPU tensors are served by the portable backend only");
+  pc_check_tensor(q_pad, "q_pad", on_gpu);
+  pc_check_tensor(pos, "positions", on_gpu);
+  pc_check_tensor(wts, "packed weights", on_gpu);
+  TORCH_CHECK(k >= 1 && k <= pc::MAX_K, "pc_codec: k must be in [1, ",
+              pc::MAX_K, "]");
+  TORCH_CHECK(L >= 1 && L <= pc::MAX_L, "pc_codec: L must be in [1, ",
+              pc::MAX_L, "]");
+  TORCH_CHECK(q_pad.scalar_type() == torch::kFloat32 && q_pad.dim() == 4 &&
+                  q_pad.size(1) > 4 && q_pad.size(2) > 8 && q_pad.size(3) > 8,
+              "pc_codec: q_pad must be fp32 (B, C+4, H+8, W+8)");
+  TORCH_CHECK(q_pad.size(0) >= 1 && q_pad.size(0) <= PC_MAX_B,
+              "pc_codec: batch size must be in [1, ", PC_MAX_B, "]");
+  TORCH_CHECK(pos.scalar_type() == torch::kInt32 && pos.dim() == 2 &&
+                  pos.size(1) == 3,
+              "pc_codec: positions must be int32 (n, 3)");
+  TORCH_CHECK(wts.scalar_type() == torch::kFloat32 &&
+                  wts.numel() == (int64_t)pc::packed_numel((int)k, (int)L),
+              "pc_codec: packed weights have the wrong size");
+  if (on_gpu) return;  // the kernels test every position themselves
+  const int C = (int)q_pad.size(1) - 4, H = (int)q_pad.size(2) - 8,
+            W = (int)q_pad.size(3) - 8;
+  const int* p = pos.data_ptr<int>();
+  for (int64_t i = 0; i < pos.size(0); ++i)
+    TORCH_CHECK(p[3 * i] >= 0 && p[3 * i] < C && p[3 * i + 1] >= 0 &&
+                    p[3 * i + 1] < H && p[3 * i + 2] >= 0 && p[3 * i + 2] < W,
+                "pc_codec host: position ", i, " outside the volume");
 }
 
-// Batch forms of the three host functions: q_pad (B, C+4, H+8, W+8), one
-// position list. The bytes are those of B single-image calls.
-std::tuple<torch::Tensor, torch::Tensor> pc_freqs_batch_host(
-    torch::Tensor q_pad, torch::Tensor pos, torch::Tensor wts, int64_t k,
-    int64_t L) {
-  TORCH_CHECK(q_pad.dim() == 4, "pc_freqs_batch_host: q_pad must be 4-D");
-  pc_host_check(q_pad, pos, wts, k, L);
+// logits and freqs are (B, n, L).
+static void launch_pc_freqs(const torch::Tensor& q_pad, const int* pos,
+                            int64_t n, const torch::Tensor& wts, int64_t k,
+                            int64_t L, float* logits, int* freqs,
+                            bool portable) {
+  if (n == 0) return;
+  const int64_t B = q_pad.size(0);
+  const int C = (int)q_pad.size(1) - 4, H = (int)q_pad.size(2) - 8,
+            W = (int)q_pad.size(3) - 8;
+  const int kp = (int)((k + 7) / 8 * 8);
+  auto kernel = portable ? pc_freqs_kernel<true> : pc_freqs_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n, (unsigned)B), dim3(PC_THREADS),
+                     0, at::cuda::getCurrentCUDAStream(),
+                     q_pad.data_ptr<float>(), q_pad.stride(0), C, H, W, pos,
+                     wts.data_ptr<float>(), (int)k, kp, (int)L, logits, freqs);
+}
+
+// (logits, tables) of every position, both (B, n, L), after pc_check. The
+// host build skips the logits unless they are asked for (the kernel always
+// writes them) and returns an undefined tensor in their place.
+static std::tuple<torch::Tensor, torch::Tensor> pc_tables(
+    const torch::Tensor& q_pad, const torch::Tensor& pos,
+    const torch::Tensor& wts, int64_t k, int64_t L, bool portable,
+    bool want_logits) {
+  const bool on_gpu = q_pad.is_cuda();
   const int64_t B = q_pad.size(0), n = pos.size(0);
-  auto logits = torch::empty({B, n, L}, q_pad.options());
+  torch::Tensor logits;
+  if (on_gpu || want_logits) logits = torch::empty({B, n, L}, q_pad.options());
   auto freqs = torch::empty({B, n, L}, pos.options());
-  pc_host_eval_batch(pc_host_args(q_pad, pos, wts, k, L,
-                                  logits.data_ptr<float>(),
-                                  freqs.data_ptr<int>()),
-                     B, q_pad.stride(0), n, 0, n);
+  if (on_gpu)
+    launch_pc_freqs(q_pad, pos.data_ptr<int>(), n, wts, k, L,
+                    logits.data_ptr<float>(), freqs.data_ptr<int>(), portable);
+  else
+    pc_host_eval(pc_host_args(q_pad, pos, wts, k, L,
+                              want_logits ? logits.data_ptr<float>() : nullptr,
+                              freqs.data_ptr<int>()),
+                 B, q_pad.stride(0), n, 0, n);
   return {logits, freqs};
 }
 
-// (B, 8 + 3n + 16) bytes, the layout of the device encoder: row b holds the
-// little-endian payload length of image b, then its payload.
-torch::Tensor pc_encode_batch_host(torch::Tensor q_pad, torch::Tensor pos,
-                                   torch::Tensor syms, torch::Tensor wts,
-                                   int64_t k, int64_t L) {
-  TORCH_CHECK(q_pad.dim() == 4, "pc_encode_batch_host: q_pad must be 4-D");
-  pc_host_check(q_pad, pos, wts, k, L);
+std::tuple<torch::Tensor, torch::Tensor> pc_freqs(torch::Tensor q_pad,
+                                                  torch::Tensor pos,
+                                                  torch::Tensor wts, int64_t k,
+                                                  int64_t L, bool portable) {
+  pc_check(q_pad, pos, wts, k, L, q_pad.is_cuda(), portable);
+  return pc_tables(q_pad, pos, wts, k, L, portable, true);
+}
+
+// Device range encoder: syms (B, n), freqs (B, n, L) -> (B, 8 + 3n + 16)
+// bytes: row b holds the little-endian payload length of image b, then its
+// payload.
+torch::Tensor rc_encode(torch::Tensor syms, torch::Tensor freqs) {
+  CHECK_CUDA_CONTIG(syms);
+  CHECK_CUDA_CONTIG(freqs);
+  TORCH_CHECK(syms.scalar_type() == torch::kInt32 && syms.dim() == 2 &&
+                  syms.size(0) >= 1 && syms.size(0) <= PC_MAX_B,
+              "rc_encode: symbols must be int32 (B, n), B in [1, ", PC_MAX_B,
+              "]");
+  TORCH_CHECK(freqs.scalar_type() == torch::kInt32 && freqs.dim() == 3 &&
+                  freqs.size(0) == syms.size(0) &&
+                  freqs.size(1) == syms.size(1) && freqs.size(2) >= 1 &&
+                  freqs.size(2) <= rc::MAX_L,
+              "rc_encode: tables must be int32 (B, n, L<=16)");
+  const int64_t B = syms.size(0), n = syms.size(1), L = freqs.size(2);
+  const int64_t cap = 3 * n + 16;
+  auto out = torch::empty({B, 8 + cap}, syms.options().dtype(torch::kUInt8));
+  hipLaunchKernelGGL(rc_encode_kernel, dim3((unsigned)B), dim3(RC_CHUNK), 0,
+                     at::cuda::getCurrentCUDAStream(), syms.data_ptr<int>(),
+                     freqs.data_ptr<int>(), n, (int)L,
+                     out.data_ptr<uint8_t>(), (uint64_t)cap);
+  return out;
+}
+
+// Context model + range encoder: syms (B, n) -> the rows of rc_encode, on
+// either device.
+torch::Tensor pc_encode(torch::Tensor q_pad, torch::Tensor pos,
+                        torch::Tensor syms, torch::Tensor wts, int64_t k,
+                        int64_t L, bool portable) {
+  const bool on_gpu = q_pad.is_cuda();
+  pc_check(q_pad, pos, wts, k, L, on_gpu, portable);
+  pc_check_tensor(syms, "symbols", on_gpu);
   const int64_t B = q_pad.size(0), n = pos.size(0);
-  TORCH_CHECK(!syms.is_cuda() && syms.is_contiguous() &&
-                  syms.scalar_type() == torch::kInt32 && syms.dim() == 2 &&
+  TORCH_CHECK(syms.scalar_type() == torch::kInt32 && syms.dim() == 2 &&
                   syms.size(0) == B && syms.size(1) == n,
-              "pc_encode_batch_host: int32 (B, n) symbols, one per position "
-              "and image");
-  auto freqs = torch::empty({B, n, L}, pos.options());
-  pc_host_eval_batch(pc_host_args(q_pad, pos, wts, k, L, nullptr,
-                                  freqs.data_ptr<int>()),
-                     B, q_pad.stride(0), n, 0, n);
+              "pc_encode: symbols must be int32 (B, n), one per position and "
+              "image");
+  auto freqs = std::get<1>(pc_tables(q_pad, pos, wts, k, L, portable, false));
+  if (on_gpu) return rc_encode(syms, freqs);
   const int64_t cap = 3 * n + 16;
   auto out = torch::zeros({B, 8 + cap}, torch::kUInt8);
   const int* sp = syms.data_ptr<int>();
@@ -888,64 +626,181 @@ torch::Tensor pc_encode_batch_host(torch::Tensor q_pad, torch::Tensor pos,
   return out;
 }
 
-// Wavefront decode of B images on the host: wave i covers
-// pos[offsets[i], offsets[i+1]) in every image, image b's payload is
-// data[data_offs[b], data_offs[b+1]). q_pad is filled in place; returns the
-// (B, C, H, W) int64 symbols.
-torch::Tensor pc_decode_batch_host(torch::Tensor q_pad, torch::Tensor pos,
-                                   std::vector<int64_t> offsets,
-                                   torch::Tensor wts, int64_t k, int64_t L,
-                                   torch::Tensor data,
-                                   std::vector<int64_t> data_offs,
-                                   torch::Tensor centers) {
-  TORCH_CHECK(q_pad.dim() == 4, "pc_decode_batch_host: q_pad must be 4-D");
-  pc_host_check(q_pad, pos, wts, k, L);
-  TORCH_CHECK(!data.is_cuda() && data.is_contiguous() &&
-                  data.scalar_type() == torch::kUInt8 && data.dim() == 1,
-              "pc_decode_host: data must be CPU uint8 (len,)");
-  TORCH_CHECK(!centers.is_cuda() && centers.is_contiguous() &&
-                  centers.scalar_type() == torch::kFloat32 &&
-                  centers.numel() == L,
-              "pc_decode_host: centers must be CPU fp32 (L,)");
-  const int64_t B = q_pad.size(0), n = pos.size(0);
-  TORCH_CHECK((int64_t)data_offs.size() == B + 1 &&
-                  pcb::offsets_ok(data_offs.data(), B, data.numel()),
-              "pc_decode_host: payload offsets must be B+1 values running "
-              "from 0 to len(data) without decreasing");
-  TORCH_CHECK(offsets.size() >= 1 && offsets.front() == 0 &&
-                  offsets.back() == n,
-              "pc_decode_host: wave offsets must run from 0 to n");
-  for (size_t i = 1; i < offsets.size(); ++i)
-    TORCH_CHECK(offsets[i] >= offsets[i - 1],
-                "pc_decode_host: wave offsets must not decrease");
-  const int C = (int)q_pad.size(1) - 4, H = (int)q_pad.size(2) - 8,
-            W = (int)q_pad.size(3) - 8;
-  auto out = torch::zeros({B, C, H, W}, torch::kInt64);
+// B decoder states, started by one launch. offs is null for a single image
+// (B = 1, the whole of data) and (B + 1) int64 on the device otherwise.
+static torch::Tensor decode_state(const torch::Tensor& data,
+                                  const int64_t* offs, int64_t B) {
+  auto state = torch::empty({B, (int64_t)(sizeof(rc::State) / 8)},
+                            data.options().dtype(torch::kInt64));
+  hipLaunchKernelGGL(rc_decode_init_kernel, dim3((unsigned)((B + 63) / 64)),
+                     dim3(64), 0, at::cuda::getCurrentCUDAStream(),
+                     reinterpret_cast<rc::State*>(state.data_ptr<int64_t>()),
+                     data.data_ptr<uint8_t>(), (uint64_t)data.numel(), offs,
+                     B);
+  return state;
+}
+
+// Decode n symbols against given tables (n, L) in one launch.
+torch::Tensor rc_decode(torch::Tensor data, torch::Tensor freqs) {
+  CHECK_CUDA_CONTIG(data);
+  CHECK_CUDA_CONTIG(freqs);
+  TORCH_CHECK(data.scalar_type() == torch::kUInt8 && data.dim() == 1,
+              "rc_decode: data must be uint8 (len,)");
+  TORCH_CHECK(freqs.scalar_type() == torch::kInt32 && freqs.dim() == 2 &&
+                  freqs.size(1) >= 1 && freqs.size(1) <= rc::MAX_L,
+              "rc_decode: tables must be int32 (n, L<=16)");
+  const int64_t n = freqs.size(0), L = freqs.size(1);
+  auto out = torch::zeros({n}, freqs.options().dtype(torch::kInt64));
   if (n == 0) return out;
-  auto freqs = torch::empty({B, n, L}, pos.options());
-  const PcHostArgs a = pc_host_args(q_pad, pos, wts, k, L, nullptr,
-                                    freqs.data_ptr<int>());
-  const int64_t q_stride = q_pad.stride(0);
-  const pcb::DecodeArgs d{B, n, (int)L, C, H, W, pos.data_ptr<int>(),
-                          freqs.data_ptr<int>(), data.data_ptr<uint8_t>(),
-                          data_offs.data(), centers.data_ptr<float>(),
-                          q_pad.data_ptr<float>(), out.data_ptr<int64_t>()};
-  pcb::decode_batch(d, offsets, [&](int64_t lo, int64_t hi) {
-    pc_host_eval_batch(a, B, q_stride, n, lo, hi);
-  });
+  auto state = decode_state(data, nullptr, 1);
+  hipLaunchKernelGGL(rc_decode_wave_kernel, dim3(1), dim3(RC_CHUNK), 0,
+                     at::cuda::getCurrentCUDAStream(),
+                     reinterpret_cast<rc::State*>(state.data_ptr<int64_t>()),
+                     data.data_ptr<uint8_t>(), (uint64_t)data.numel(),
+                     (const int64_t*)nullptr, freqs.data_ptr<int>(),
+                     (const int*)nullptr, n, (int)L, (const float*)nullptr,
+                     (float*)nullptr, (int64_t)0, 0, 0, 0,
+                     out.data_ptr<int64_t>(), n);
   return out;
 }
 
-// The single image of pc_decode_batch_host: (C+4, H+8, W+8) -> (C, H, W).
-torch::Tensor pc_decode_host(torch::Tensor q_pad, torch::Tensor pos,
-                             std::vector<int64_t> offsets, torch::Tensor wts,
-                             int64_t k, int64_t L, torch::Tensor data,
-                             torch::Tensor centers) {
-  TORCH_CHECK(q_pad.dim() == 3,
-              "pc_codec: q_pad must be fp32 (C+4, H+8, W+8)");
-  return pc_decode_batch_host(q_pad.unsqueeze(0), pos, offsets, wts, k, L,
-                              data, {0, data.numel()}, centers)
-      .squeeze(0);
+// What a decode takes beside pc_check's arguments: wave i covers
+// pos[offsets[i], offsets[i+1]) in every image, image b's payload is
+// data[data_offs[b], data_offs[b+1]). Returns the widest wave.
+static int64_t pc_decode_check(const std::vector<int64_t>& offsets, int64_t n,
+                               const torch::Tensor& data,
+                               const std::vector<int64_t>& data_offs,
+                               int64_t B, const torch::Tensor& centers,
+                               int64_t L, bool on_gpu) {
+  pc_check_tensor(data, "data", on_gpu);
+  pc_check_tensor(centers, "centers", on_gpu);
+  TORCH_CHECK(data.scalar_type() == torch::kUInt8 && data.dim() == 1,
+              "pc_decode: data must be uint8 (len,)");
+  TORCH_CHECK(centers.scalar_type() == torch::kFloat32 &&
+                  centers.numel() == L,
+              "pc_decode: centers must be fp32 (L,)");
+  TORCH_CHECK((int64_t)data_offs.size() == B + 1 &&
+                  pcb::offsets_ok(data_offs.data(), B, data.numel()),
+              "pc_decode: payload offsets must be B+1 values running from 0 "
+              "to len(data) without decreasing");
+  TORCH_CHECK(offsets.size() >= 1 && offsets.front() == 0 &&
+                  offsets.back() == n,
+              "pc_decode: wave offsets must run from 0 to n");
+  int64_t maxw = 0;
+  for (size_t i = 1; i < offsets.size(); ++i) {
+    TORCH_CHECK(offsets[i] >= offsets[i - 1],
+                "pc_decode: wave offsets must not decrease");
+    maxw = std::max(maxw, offsets[i] - offsets[i - 1]);
+  }
+  return maxw;
+}
+
+// Wavefront decode of B images; q_pad is filled in place; returns the
+// (B, C, H, W) int64 symbols. GPU: one state init, then two launches per
+// wave on the current stream whatever B is, with no host synchronisation:
+// pc_freqs over (positions of the wave, images), rc_decode_wave with one
+// workgroup per image. B = 1 passes no offsets to the kernels and copies
+// none. CPU: pcb::decode_batch over the host build of the model.
+torch::Tensor pc_decode(torch::Tensor q_pad, torch::Tensor pos,
+                        std::vector<int64_t> offsets, torch::Tensor wts,
+                        int64_t k, int64_t L, torch::Tensor data,
+                        std::vector<int64_t> data_offs, torch::Tensor centers,
+                        bool portable) {
+  const bool on_gpu = q_pad.is_cuda();
+  pc_check(q_pad, pos, wts, k, L, on_gpu, portable);
+  const int64_t B = q_pad.size(0), n = pos.size(0);
+  const int64_t maxw =
+      pc_decode_check(offsets, n, data, data_offs, B, centers, L, on_gpu);
+  const int C = (int)q_pad.size(1) - 4, H = (int)q_pad.size(2) - 8,
+            W = (int)q_pad.size(3) - 8;
+  auto out = torch::zeros({B, C, H, W}, pos.options().dtype(torch::kInt64));
+  if (n == 0) return out;
+  if (!on_gpu) {
+    auto freqs = torch::empty({B, n, L}, pos.options());
+    const PcHostArgs a = pc_host_args(q_pad, pos, wts, k, L, nullptr,
+                                      freqs.data_ptr<int>());
+    const int64_t q_stride = q_pad.stride(0);
+    const pcb::DecodeArgs d{B, n, (int)L, C, H, W, pos.data_ptr<int>(),
+                            freqs.data_ptr<int>(), data.data_ptr<uint8_t>(),
+                            data_offs.data(), centers.data_ptr<float>(),
+                            q_pad.data_ptr<float>(), out.data_ptr<int64_t>()};
+    pcb::decode_batch(d, offsets, [&](int64_t lo, int64_t hi) {
+      pc_host_eval(a, B, q_stride, n, lo, hi);
+    });
+    return out;
+  }
+  auto logits = torch::empty({B, maxw, L}, q_pad.options());
+  auto freqs = torch::empty({B, maxw, L}, pos.options());
+  torch::Tensor offs_dev;
+  const int64_t* offs = nullptr;
+  if (B > 1) {
+    offs_dev = torch::tensor(data_offs, torch::kInt64).to(data.device());
+    offs = offs_dev.data_ptr<int64_t>();
+  }
+  auto state = decode_state(data, offs, B);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const int* p = pos.data_ptr<int>();
+  for (size_t i = 1; i < offsets.size(); ++i) {
+    const int64_t o = offsets[i - 1], nw = offsets[i] - o;
+    if (nw == 0) continue;
+    // the wave's tables are compact: (B, nw, L) at the head of the buffers
+    launch_pc_freqs(q_pad, p + 3 * o, nw, wts, k, L, logits.data_ptr<float>(),
+                    freqs.data_ptr<int>(), portable);
+    hipLaunchKernelGGL(rc_decode_wave_kernel, dim3((unsigned)B),
+                       dim3(RC_CHUNK), 0, stream,
+                       reinterpret_cast<rc::State*>(state.data_ptr<int64_t>()),
+                       data.data_ptr<uint8_t>(), (uint64_t)data.numel(), offs,
+                       freqs.data_ptr<int>(), p + 3 * o, nw, (int)L,
+                       centers.data_ptr<float>(), q_pad.data_ptr<float>(),
+                       q_pad.stride(0), C, H, W, out.data_ptr<int64_t>(),
+                       (int64_t)C * H * W);
+  }
+  return out;
+}
+
+// Host build of the coder step functions alone (CPU tensors, given tables),
+// for the tests: (n,) symbols -> the payload bytes, no length prefix.
+torch::Tensor rc_encode_host(torch::Tensor syms, torch::Tensor freqs) {
+  TORCH_CHECK(!syms.is_cuda() && !freqs.is_cuda() && syms.is_contiguous() &&
+                  freqs.is_contiguous(),
+              "rc_encode_host: CPU contiguous tensors");
+  TORCH_CHECK(syms.scalar_type() == torch::kInt32 && syms.dim() == 1 &&
+                  freqs.scalar_type() == torch::kInt32 && freqs.dim() == 2 &&
+                  freqs.size(0) == syms.size(0) && freqs.size(1) >= 1 &&
+                  freqs.size(1) <= rc::MAX_L,
+              "rc_encode_host: int32 (n,) symbols and (n, L<=16) tables");
+  const int64_t n = syms.size(0), L = freqs.size(1);
+  const int64_t cap = 3 * n + 16;
+  auto out = torch::zeros({cap}, torch::kUInt8);
+  const int64_t len = (int64_t)pcb::encode_row(
+      syms.data_ptr<int>(), freqs.data_ptr<int>(), n, (int)L,
+      out.data_ptr<uint8_t>(), (uint64_t)cap);
+  TORCH_CHECK(len <= cap, "rc_encode_host: stream overran ", cap, " bytes");
+  return out.slice(0, 0, len).clone();
+}
+
+torch::Tensor rc_decode_host(torch::Tensor data, torch::Tensor freqs) {
+  TORCH_CHECK(!data.is_cuda() && !freqs.is_cuda() && data.is_contiguous() &&
+                  freqs.is_contiguous(),
+              "rc_decode_host: CPU contiguous tensors");
+  TORCH_CHECK(data.scalar_type() == torch::kUInt8 && data.dim() == 1 &&
+                  freqs.scalar_type() == torch::kInt32 && freqs.dim() == 2 &&
+                  freqs.size(1) >= 1 && freqs.size(1) <= rc::MAX_L,
+              "rc_decode_host: uint8 data and int32 (n, L<=16) tables");
+  const int64_t n = freqs.size(0), L = freqs.size(1);
+  auto out = torch::zeros({n}, torch::kInt32);
+  const rc::ByteSource src{data.data_ptr<uint8_t>(), (uint64_t)data.numel()};
+  rc::State st;
+  rc::decode_start(st, src);
+  const int* fp = freqs.data_ptr<int>();
+  int* op = out.data_ptr<int>();
+  uint32_t cum[rc::MAX_L + 1];
+  for (int64_t i = 0; i < n; ++i) {
+    rc::cumulate(fp + i * L, (int)L, cum);
+    op[i] = rc::decode_cum(st, src, cum, (int)L);
+  }
+  return out;
 }
 
 }  // namespace dsin
+

@@ -181,7 +181,9 @@ def test_device_coder_matches_python_coder(dev):
     pos, _ = _positions(shape)
     _, fr = ops.pc_freqs(pc, q, pos)
     syms = _at(symbols, pos).to(torch.int32)
-    buf = ops._require_ext("rc_encode")(syms.to(dev), fr).cpu().numpy()
+    rows = ops._require_ext("rc_encode")(syms.to(dev)[None], fr[None])
+    assert rows.shape == (1, 8 + 3 * len(syms) + 16)
+    buf = rows[0].cpu().numpy()
     n = int.from_bytes(buf[:8].tobytes(), "little")
     got = buf[8:8 + n].tobytes()
     want = encode_with_freqs(syms.tolist(), iter(fr.cpu().numpy().astype(np.int64)))

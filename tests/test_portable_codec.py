@@ -181,6 +181,21 @@ def test_golden_stream():
     assert encode_symbols(pc, centers, symbols, backend="portable") == stream
 
 
+def test_extension_has_one_set_of_codec_entry_points():
+    """The context model is reached through three entry points that take a
+    batch and dispatch on the device; no per-device or single-image twin of
+    them is left in the built extension."""
+    ext = ops._try_load_ext()
+    assert ext is not None
+    for name in ("pc_freqs", "pc_encode", "pc_decode"):
+        assert hasattr(ext, name), name
+    for name in ("pc_freqs_batch", "rc_encode_batch", "pc_encode_batch",
+                 "pc_decode_batch", "pc_freqs_batch_host",
+                 "pc_encode_batch_host", "pc_decode_batch_host",
+                 "pc_freqs_host", "pc_encode_host", "pc_decode_host"):
+        assert not hasattr(ext, name), name
+
+
 def test_cpu_without_extension_raises_runtime_error(monkeypatch):
     pc = P.make_pc(6, 8)
     centers = P.centers_of(6)

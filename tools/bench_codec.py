@@ -17,6 +17,11 @@ issues (encode: pc_freqs + rc_encode; decode: one state init plus pc_freqs
 L=6) with seeded random weights; every decode is checked against the
 symbols.
 
+With the hip and portable backends encode_symbols / decode_symbols are a
+batch of one through the batch functions (ops.pc_encode_batch /
+pc_decode_batch and the extension's pc_encode / pc_decode, which take
+(B, ...) only), so the single-image lines time that path at B = 1.
+
 --backend torch calls encode_symbols / decode_symbols without the backend
 argument, so the tool also runs on a commit that predates it.
 
