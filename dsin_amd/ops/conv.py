@@ -2,8 +2,8 @@
 
 Covers every 2D conv in DSIN: direct conv with any
 stride/dilation, transposed conv, and the full backward — via ONE device
-kernel pair (conv_fwd gather-GEMM + conv_wrw) plus torch-differentiable
-geometry transforms:
+kernel pair (conv_fwd_kernel gather-GEMM + conv_wrw_kernel) plus
+torch-differentiable geometry transforms:
 
   * forward flattens the weight to (Co, K=(ci,r,s)); the kernel computes
     out[pixel][cout] = sum_k xv[coords(pixel) + tap(k)] * w[cout][k], where
@@ -11,10 +11,11 @@ geometry transforms:
     packed coordinate tables against the raw tensor and produces zeros for
     the pad ring and stuff holes (no padded buffer, no pad kernel, no
     extra HBM round trip — round-1's pad_stuff path cost ~2 ms/step);
-  * backward-data is the transposed virtual geometry on the raw dy
-    ((st', sv', pads') = (sv, st, (k-1)*dil - pads)) with spatially-rotated
-    ci<->co-swapped weights; stride-1 3x3 shapes take the direct LDS-halo
-    kernel (forward and backward) with its own virtual pad;
+  * backward-data is the SAME gather (_gather) on the raw dy with the
+    transposed virtual geometry ((st', sv', pads') = (sv, st, (k-1)*dil -
+    pads)) and spatially-rotated ci<->co-swapped weights; _route picks the
+    kernel of either one: stride-1 3x3 shapes take the direct LDS-halo
+    kernel with its own virtual pad, stuffed-by-2 gathers four dense phases;
   * backward-weight is the conv_wrw kernel (per-pixel-chunk fp32 partial
     slices reduced with one sum — no atomics), same virtual staging;
   * the padded/rotated W panel is one fused kernel (wmat_make), cached
@@ -29,7 +30,7 @@ CPU path falls back to torch.nn.functional (the numerics oracle).
 
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
@@ -114,8 +115,8 @@ def _plan(device, Ci: int, Hp: int, Wp: int, kh: int, kw: int, stride: int,
     return p
 
 
-def _plan_v2(device, M: int, K: int, WO: int, stride: int, dil: int,
-             kh: int, kw: int):
+def _packed_plan(device, M: int, K: int, WO: int, stride: int, dil: int,
+                 kh: int, kw: int):
     """Packed-coordinate tables for the virtual-pad gather path."""
     key = ("v2", device.index, M, K, WO, stride, dil, kh, kw)
     p = _PLANS.get(key)
@@ -171,17 +172,6 @@ def _phase_plans(device, HO: int, WO: int, kh: int, kw: int, Cin: int,
     return plans
 
 
-def _dummy_tables(device):
-    """Placeholder table args for the direct-kernel branch (unused there)."""
-    key = ("dummy", device.index)
-    p = _PLANS.get(key)
-    if p is None:
-        t = torch.zeros(1, dtype=torch.int32, device=device)
-        p = (t, t)
-        _PLANS[key] = p
-    return p
-
-
 def _wmat(w1: torch.Tensor, fp8: bool = False, direct: bool = False,
           khw: int = 9) -> torch.Tensor:
     """(Co, K) any-dtype -> bf16 (or e4m3-as-uint8) zero-padded to
@@ -229,6 +219,82 @@ def _act_grad(dy: torch.Tensor, y_act, act: int) -> torch.Tensor:
     return dy
 
 
+class _Geom(NamedTuple):
+    """Geometry of one virtual-pad gather: conv stride st over an input
+    zero-stuffed by sv, dilation dil, kh x kw taps, top/left pads pt/pl."""
+    st: int
+    sv: int
+    dil: int
+    kh: int
+    kw: int
+    pt: int
+    pl: int
+
+    def transposed(self) -> "_Geom":
+        """The backward-data gather on dy (with the rotated panel)."""
+        return _Geom(self.sv, self.st, self.dil, self.kh, self.kw,
+                     (self.kh - 1) * self.dil - self.pt,
+                     (self.kw - 1) * self.dil - self.pl)
+
+
+def _route(Cin: int, g: _Geom, rotated: bool, direct_ok: bool) -> str:
+    """Which kernels run one gather over Cin input channels: "direct3" (3x3
+    stride-1 LDS-halo kernel: equal pads of at least 1), "direct5" (5x5
+    stride-2 LDS-halo kernel, forward panel only), "phase" (stuffed by 2:
+    four dense sub-convs, see _phase_plans) or the plain "gather". rotated:
+    the backward-data panel; direct_ok: False for conv-transpose forward.
+    Touches no tensor."""
+    if direct_ok and g.sv == 1 and g.dil == 1 and Cin % 64 == 0:
+        if (g.st == 1 and g.kh == 3 and g.kw == 3 and g.pt == g.pl
+                and g.pt >= 1):
+            return "direct3"
+        if (g.st == 2 and g.kh == 5 and g.kw == 5 and not rotated
+                and _DIRECT5):
+            return "direct5"
+    if g.sv == 2 and g.dil == 1:
+        return "phase"
+    return "gather"
+
+
+def _gather(x, w1, g: _Geom, N: int, HO: int, WO: int, bias, act: int,
+            rotated: bool, direct_ok: bool):
+    """One routed gather of x (B, Cin, H, W) into (B, N, HO, WO). w1 is
+    the forward weight (Co, Ci*kh*kw); rotated selects its backward-data
+    panels (taps reversed, ci<->co swapped), for x = dy."""
+    B, Cin = x.shape[:2]
+    khw = g.kh * g.kw
+    route = _route(Cin, g, rotated, direct_ok)
+    if route in ("direct3", "direct5"):
+        wm = (_wmat_rot(w1, khw, True) if rotated
+              else _wmat(w1, direct=True, khw=khw))
+        return _require_ext("conv_direct")(x, wm, bias, N, HO, WO, act, g.pt,
+                                           g.kh)
+    ext = _require_ext("conv_gather")
+    if route == "gather":
+        mpack, kpack = _packed_plan(x.device, HO * WO, Cin * khw, WO, g.st,
+                                    g.dil, g.kh, g.kw)
+        wm = _wmat_rot(w1, khw) if rotated else _wmat(w1)
+        return ext(x, wm, bias, mpack, kpack, N, Cin * khw, HO, WO, act,
+                   g.st, g.sv, g.pt, g.pl)
+    # 4 dense stride-1 phase sub-convs writing strided into one full-grid
+    # output, each with a column-gather of the (rotated) panel. A phase with
+    # no matching taps (k=1 dims) is mathematically zero but never written
+    # -> zero-init unless all 4 phases run.
+    pg = _require_ext("panel_gather")
+    plans = _phase_plans(x.device, HO, WO, g.kh, g.kw, Cin, g.pt, g.pl)
+    alloc = torch.empty if len(plans) == 4 else torch.zeros
+    y = alloc(B, N, HO, WO, dtype=torch.bfloat16, device=x.device)
+    tag = "phr" if rotated else "ph"
+    for p_ in plans:
+        wp = _wmat_cache(
+            w1, (tag, p_["a"], p_["b"], g.kh, g.kw),
+            lambda p_=p_: pg(_wmat_rot(w1, khw) if rotated
+                             else w1.contiguous(), p_["ktab"]))
+        ext(x, wp, bias, p_["mpack"], p_["kpack"], N, p_["Kp"], p_["nh"],
+            p_["nw"], act, 1, 1, p_["ptp"], p_["plp"], y, p_["a"], p_["b"], 2)
+    return y
+
+
 class _GatherConvFn(torch.autograd.Function):
     """Virtual-pad gather conv:
         y[b, co, oh, ow] = sum_{ci,r,s} xv[b, ci, oh*st + r*d, ow*st + s*d]
@@ -241,53 +307,20 @@ class _GatherConvFn(torch.autograd.Function):
     (st', sv', pads') = (sv, st, (k-1)*dil - pads) with rotated weights."""
 
     @staticmethod
-    def forward(ctx, x, w1, bias, st, sv, dil, kh, kw, pt, pl, HO, WO, act,
-                direct):
-        ext_fwd = _require_ext("conv_fwd")
-        assert sv in (1, 2), "virtual stuff supports stride 1/2 only"
-        B, Ci, H, W = x.shape
-        Co, K = w1.shape
+    def forward(ctx, x, w1, bias, g, HO, WO, act, direct_ok):
+        assert g.sv in (1, 2), "virtual stuff supports stride 1/2 only"
         bias32 = bias.float().contiguous() if bias is not None else None
-        if direct == 2:
-            dt = _dummy_tables(x.device)
-            y = ext_fwd(x, _wmat(w1, direct=True, khw=25), bias32, dt[0],
-                        dt[1], Co, K, HO, WO, act, 2, 2, pt, 0, 0, 0, 1,
-                        None, 0, 0, 1, WO)
-        elif direct:
-            dt = _dummy_tables(x.device)
-            y = ext_fwd(x, _wmat(w1, direct=True), bias32, dt[0], dt[1], Co,
-                        K, HO, WO, act, 1, 1, pt, 0, 0, 0, 1,
-                        None, 0, 0, 1, WO)
-        elif sv == 2 and dil == 1:
-            # conv-transpose: 4 dense stride-1 phase sub-convs (see
-            # _phase_plans) writing strided into one full-grid output.
-            # A phase with no matching taps (k=1 dims) is mathematically
-            # zero but never written -> zero-init unless all 4 phases run.
-            pg = _require_ext("panel_gather")
-            plans = _phase_plans(x.device, HO, WO, kh, kw, Ci, pt, pl)
-            alloc = torch.empty if len(plans) == 4 else torch.zeros
-            y = alloc(B, Co, HO, WO, dtype=torch.bfloat16, device=x.device)
-            for p_ in plans:
-                wp = _wmat_cache(
-                    w1, ("ph", p_["a"], p_["b"], kh, kw),
-                    lambda p_=p_: pg(w1.contiguous(), p_["ktab"]))
-                ext_fwd(x, wp, bias32, p_["mpack"], p_["kpack"], Co,
-                        p_["Kp"], p_["nh"], p_["nw"], act, 1, 0, 0, 1,
-                        p_["ptp"], p_["plp"], 1, y, p_["a"], p_["b"], 2, WO)
-        else:
-            mpack, kpack = _plan_v2(x.device, HO * WO, K, WO, st, dil, kh, kw)
-            y = ext_fwd(x, _wmat(w1), bias32, mpack, kpack, Co, K, HO, WO,
-                        act, st, 0, 0, 1, pt, pl, sv, None, 0, 0, 1, WO)
+        y = _gather(x, w1, g, w1.shape[0], HO, WO, bias32, act, False,
+                    direct_ok)
         ctx.save_for_backward(x, w1, y if act else None)
-        ctx.meta = (st, sv, dil, kh, kw, pt, pl, HO, WO, bias is not None, act)
+        ctx.meta = (g, HO, WO, bias is not None, act)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w1, y_act = ctx.saved_tensors
-        st, sv, dil, kh, kw, pt, pl, HO, WO, has_bias, act = ctx.meta
-        ext_fwd = _require_ext("conv_fwd")
-        ext_wrw = _require_ext("conv_wrw")
+        g, HO, WO, has_bias, act = ctx.meta
+        ext_wrw = _require_ext("conv_wrw_gather")
         B, Ci, H, W = x.shape
         Co, K = w1.shape
 
@@ -295,65 +328,33 @@ class _GatherConvFn(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             with torch.no_grad():
-                ptb = (kh - 1) * dil - pt
-                plb = (kw - 1) * dil - pl
-                dir_b = (sv == 1 and st == 1 and dil == 1 and kh == 3
-                         and kw == 3 and Co % 64 == 0 and ptb == plb
-                         and ptb >= 1)
-                if dir_b:
-                    dt = _dummy_tables(x.device)
-                    dx = ext_fwd(dy, _wmat_rot(w1, 9, True), None, dt[0],
-                                 dt[1], Ci, Co * 9, H, W, 0, 1, 1, ptb,
-                                 0, 0, 0, 1, None, 0, 0, 1, W)
-                elif st == 2 and dil == 1:
-                    # stride-2 backward-data: phase sub-convs over raw dy
-                    # with per-phase column-gathers of the rotated panel
-                    pg = _require_ext("panel_gather")
-                    rot = _wmat_rot(w1, kh * kw)
-                    plans_b = _phase_plans(dy.device, H, W, kh, kw, Co,
-                                           ptb, plb)
-                    alloc = torch.empty if len(plans_b) == 4 else torch.zeros
-                    dx = alloc(B, Ci, H, W, dtype=torch.bfloat16,
-                               device=x.device)
-                    for p_ in plans_b:
-                        wp = _wmat_cache(
-                            w1, ("phr", p_["a"], p_["b"], kh, kw),
-                            lambda p_=p_: pg(rot, p_["ktab"]))
-                        ext_fwd(dy, wp, None, p_["mpack"], p_["kpack"], Ci,
-                                p_["Kp"], p_["nh"], p_["nw"], 0, 1, 0, 0, 1,
-                                p_["ptp"], p_["plp"], 1, dx, p_["a"],
-                                p_["b"], 2, W)
-                else:
-                    mb, kb = _plan_v2(dy.device, H * W, Co * kh * kw, W, sv,
-                                      dil, kh, kw)
-                    dx = ext_fwd(dy, _wmat_rot(w1, kh * kw), None, mb, kb,
-                                 Ci, Co * kh * kw, H, W, 0, sv, 0, 0,
-                                 1, ptb, plb, st, None, 0, 0, 1, W)
+                dx = _gather(dy, w1, g.transposed(), Ci, H, W, None, 0, True,
+                             True)
 
         dw1 = None
         if ctx.needs_input_grad[1]:
-            if sv == 2 and dil == 1:
+            if g.sv == 2 and g.dil == 1:
                 # conv-transpose weight grad by phases: each phase's compact
                 # dW lands in its own tap columns (disjoint across phases)
                 dw32 = torch.zeros(Co, K, dtype=torch.float32,
                                    device=x.device)
-                for p_ in _phase_plans(x.device, HO, WO, kh, kw, Ci, pt, pl):
+                for p_ in _phase_plans(x.device, HO, WO, g.kh, g.kw, Ci,
+                                       g.pt, g.pl):
                     dy_p = dy[:, :, p_["a"]::2, p_["b"]::2].contiguous()
                     dwp = ext_wrw(x, dy_p, p_["mpack"], p_["kpack"], Co,
-                                  p_["Kp"], p_["nw"], True, 1, 1,
-                                  p_["ptp"], p_["plp"], 1)
+                                  p_["Kp"], p_["nw"], 1, p_["ptp"], p_["plp"])
                     dw32.index_copy_(1, p_["ktab64"], dwp)
                 dw1 = dw32.to(w1.dtype)
             else:
-                mpack, kpack = _plan_v2(x.device, HO * WO, K, WO, st, dil,
-                                        kh, kw)
-                dw1 = ext_wrw(x, dy, mpack, kpack, Co, K, WO, st == 1,
-                              1, st, pt, pl, sv).to(w1.dtype)
+                assert g.sv == 1, "the weight gradient has no stuffed staging"
+                mpack, kpack = _packed_plan(x.device, HO * WO, K, WO, g.st,
+                                            g.dil, g.kh, g.kw)
+                dw1 = ext_wrw(x, dy, mpack, kpack, Co, K, WO, g.st, g.pt,
+                              g.pl).to(w1.dtype)
 
         dbias = (dy.sum(dim=(0, 2, 3), dtype=torch.float32)
                  if has_bias else None)
-        return (dx, dw1, dbias, None, None, None, None, None, None, None,
-                None, None, None, None)
+        return dx, dw1, dbias, None, None, None, None, None
 
 
 class _GatherConvFP8Fn(torch.autograd.Function):
@@ -366,7 +367,7 @@ class _GatherConvFP8Fn(torch.autograd.Function):
     def forward(ctx, x, w1, bias, stride, dil, kh, kw, HO, WO, act, pads,
                 stuff):
         pad_fn = _require_ext("pad_stuff")
-        ext_fwd = _require_ext("conv_fwd")
+        ext_fwd = _require_ext("conv_flat")
         pl, pr, pt, pb = pads
         xbuf = pad_fn(x.contiguous(), pt, pb, pl, pr, stuff, True)
         B, Ci, Hp, Wp = xbuf.shape
@@ -374,7 +375,7 @@ class _GatherConvFP8Fn(torch.autograd.Function):
         mbase, koff = _plan(x.device, Ci, Hp, Wp, kh, kw, stride, dil, HO, WO)
         bias32 = bias.float().contiguous() if bias is not None else None
         y = ext_fwd(xbuf, _wmat(w1, fp8=True), bias32, mbase, koff, Co, K,
-                    HO, WO, act, stride, 0, 0, 0, 0, 0, 1, None, 0, 0, 1, WO)
+                    HO, WO, act, stride)
         ctx.save_for_backward(xbuf, w1, y if act else None)
         ctx.meta = (stride, dil, kh, kw, HO, WO, bias is not None, act,
                     pads, stuff, x.shape, x.dtype)
@@ -386,8 +387,8 @@ class _GatherConvFP8Fn(torch.autograd.Function):
         (stride, dil, kh, kw, HO, WO, has_bias, act, pads, stuff, xshape,
          xdtype) = ctx.meta
         pad_fn = _require_ext("pad_stuff")
-        ext_fwd = _require_ext("conv_fwd")
-        ext_wrw = _require_ext("conv_wrw")
+        ext_fwd = _require_ext("conv_flat")
+        ext_wrw = _require_ext("conv_wrw_flat")
         B, Ci, Hp, Wp = xbuf.shape
         Co, K = w1.shape
         pl, pr, pt, pb = pads
@@ -410,8 +411,7 @@ class _GatherConvFP8Fn(torch.autograd.Function):
                 mb2, ko2 = _plan(dy.device, Co, dybuf.shape[2], dybuf.shape[3],
                                  kh, kw, 1, dil, Hp, Wp)
                 dxbuf = ext_fwd(dybuf, _wmat(wrot, fp8=True), None, mb2, ko2,
-                                Ci, Co * kh * kw, Hp, Wp, 0, 1, 0, 0,
-                                0, 0, 0, 1, None, 0, 0, 1, Wp)
+                                Ci, Co * kh * kw, Hp, Wp, 0, 1)
                 _, _, H, W = xshape
                 dx = dxbuf[:, :, pt:pt + (H - 1) * stuff + 1:stuff,
                            pl:pl + (W - 1) * stuff + 1:stuff].to(xdtype)
@@ -420,8 +420,8 @@ class _GatherConvFP8Fn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             mbase, koff = _plan(xbuf.device, Ci, Hp, Wp, kh, kw, stride, dil,
                                 HO, WO)
-            dw1 = ext_wrw(xbuf, dy8, mbase, koff, Co, K, WO, stride == 1,
-                          0, 1, 0, 0, 1).to(w1.dtype)
+            dw1 = ext_wrw(xbuf, dy8, mbase, koff, Co, K, WO,
+                          stride == 1).to(w1.dtype)
 
         dbias = (dy.sum(dim=(0, 2, 3), dtype=torch.float32)
                  if has_bias else None)
@@ -486,16 +486,10 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
                                       stride, dilation, kh, kw, HO, WO, act,
                                       (padding, padding, padding, padding), 1)
     x = x.to(torch.bfloat16).contiguous()
-    direct = 0
-    if stride == 1 and dilation == 1 and kh == 3 and kw == 3 \
-            and Ci % 64 == 0 and padding >= 1:
-        direct = 1
-    elif stride == 2 and dilation == 1 and kh == 5 and kw == 5 \
-            and Ci % 64 == 0 and _DIRECT5:
-        direct = 2
-    return _GatherConvFn.apply(x, w.reshape(Co, Ci * kh * kw), bias,
-                               stride, 1, dilation, kh, kw, padding, padding,
-                               HO, WO, act, direct)
+    return _GatherConvFn.apply(
+        x, w.reshape(Co, Ci * kh * kw), bias,
+        _Geom(stride, 1, dilation, kh, kw, padding, padding), HO, WO, act,
+        True)
 
 
 def conv_transpose2d(x: torch.Tensor, w: torch.Tensor,
@@ -522,9 +516,11 @@ def conv_transpose2d(x: torch.Tensor, w: torch.Tensor,
             x, w1, bias, 1, 1, kh, kw, HO, WO, act,
             (pl_w, pl_w + output_padding, pl_h, pl_h + output_padding), stride)
     x = x.to(torch.bfloat16).contiguous()
-    # sv = stride: the zero-stuffed input exists only virtually
-    return _GatherConvFn.apply(x, w1, bias, 1, stride, 1, kh, kw, pl_h, pl_w,
-                               HO, WO, act, False)
+    # sv = stride: the zero-stuffed input exists only virtually. The forward
+    # never takes a direct kernel (the backward-data gather may).
+    return _GatherConvFn.apply(x, w1, bias,
+                               _Geom(1, stride, 1, kh, kw, pl_h, pl_w), HO,
+                               WO, act, False)
 
 
 def _act(y: torch.Tensor, act: int) -> torch.Tensor:
@@ -576,15 +572,14 @@ class _GatherConv3dFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xbuf, w1, bias, kd, kh, kw, act):
-        ext_fwd = _require_ext("conv_fwd")
+        ext_fwd = _require_ext("conv_flat")
         B, Ci, Dp, Hp, Wp = xbuf.shape
         Co, K = w1.shape
         mbase, koff, Do, Ho, Wo = _plan3d(xbuf.device, Ci, Dp, Hp, Wp, kd, kh, kw)
         bias32 = bias.float().contiguous() if bias is not None else None
         # kernel sees a 2D problem: M = Do*Ho*Wo pixels, "WO" = Wo rows
         y = ext_fwd(xbuf.view(B, Ci, Dp * Hp, Wp), _wmat(w1), bias32, mbase,
-                    koff, Co, K, Do * Ho, Wo, act, 1, 0, 0, 0, 0, 0, 1,
-                    None, 0, 0, 1, Wo)
+                    koff, Co, K, Do * Ho, Wo, act, 1)
         ctx.save_for_backward(xbuf, w1, y if act else None)
         ctx.meta = (kd, kh, kw, Do, Ho, Wo, bias is not None, act)
         return y.view(B, Co, Do, Ho, Wo)
@@ -593,8 +588,8 @@ class _GatherConv3dFn(torch.autograd.Function):
     def backward(ctx, dy):
         xbuf, w1, y_act = ctx.saved_tensors
         kd, kh, kw, Do, Ho, Wo, has_bias, act = ctx.meta
-        ext_fwd = _require_ext("conv_fwd")
-        ext_wrw = _require_ext("conv_wrw")
+        ext_fwd = _require_ext("conv_flat")
+        ext_wrw = _require_ext("conv_wrw_flat")
         B, Ci, Dp, Hp, Wp = xbuf.shape
         Co, K = w1.shape
         dy = _act_grad(dy.contiguous(), y_act, act).view(B, Co, Do, Ho, Wo)
@@ -610,8 +605,7 @@ class _GatherConv3dFn(torch.autograd.Function):
                 dxbuf = ext_fwd(dybuf.view(B, Co, -1, dybuf.shape[4]),
                                 _wmat_rot(w1, kd * kh * kw), None,
                                 mb2, ko2, Ci, Co * kd * kh * kw, Dp * Hp, Wp,
-                                0, 1, 0, 0, 0, 0, 0, 1,
-                                None, 0, 0, 1, Wp).view(B, Ci, Dp, Hp, Wp)
+                                0, 1).view(B, Ci, Dp, Hp, Wp)
 
         dw1 = None
         if ctx.needs_input_grad[1]:
@@ -619,7 +613,7 @@ class _GatherConv3dFn(torch.autograd.Function):
                                            kd, kh, kw)
             dw1 = ext_wrw(xbuf.view(B, Ci, Dp * Hp, Wp),
                           dy.view(B, Co, Do * Ho, Wo), mbase, koff, Co, K,
-                          Wo, True, 0, 1, 0, 0, 1).to(w1.dtype)
+                          Wo, True).to(w1.dtype)
 
         dbias = (dy.sum(dim=(0, 2, 3, 4), dtype=torch.float32)
                  if has_bias else None)

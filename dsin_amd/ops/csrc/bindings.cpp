@@ -27,18 +27,35 @@ std::tuple<torch::Tensor, torch::Tensor> conv_tables(
 std::tuple<torch::Tensor, torch::Tensor> conv_tables_v2(
     int64_t M, int64_t K, int64_t WO, int64_t stride, int64_t dil, int64_t kh,
     int64_t kw, torch::Device device);
-torch::Tensor conv_fwd(torch::Tensor xbuf, torch::Tensor wmat,
-                       c10::optional<torch::Tensor> bias, torch::Tensor mbase,
-                       torch::Tensor koff, int64_t N, int64_t K, int64_t HO,
-                       int64_t WO, int64_t act, int64_t stride, int64_t direct,
-                       int64_t vpad, int64_t vm, int64_t vpt, int64_t vpl,
-                       int64_t vsv, c10::optional<torch::Tensor> out_opt,
-                       int64_t oh0, int64_t ow0, int64_t ostep, int64_t wof);
+std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t> conv_fwd_variant(
+    int64_t B, int64_t M, int64_t N, int64_t WO, int64_t st, int64_t sv,
+    bool flat);
+std::tuple<int64_t, int64_t> conv_wrw_variant(int64_t WO, int64_t st,
+                                              bool flat);
+torch::Tensor conv_direct(torch::Tensor x, torch::Tensor wmat,
+                          c10::optional<torch::Tensor> bias, int64_t N,
+                          int64_t HO, int64_t WO, int64_t act, int64_t vpad,
+                          int64_t ksize);
+torch::Tensor conv_gather(torch::Tensor x, torch::Tensor wmat,
+                          c10::optional<torch::Tensor> bias,
+                          torch::Tensor mpack, torch::Tensor kpack, int64_t N,
+                          int64_t K, int64_t HO, int64_t WO, int64_t act,
+                          int64_t st, int64_t sv, int64_t pt, int64_t pl,
+                          c10::optional<torch::Tensor> out, int64_t oh0,
+                          int64_t ow0, int64_t ostep);
+torch::Tensor conv_flat(torch::Tensor xbuf, torch::Tensor wmat,
+                        c10::optional<torch::Tensor> bias,
+                        torch::Tensor mbase, torch::Tensor koff, int64_t N,
+                        int64_t K, int64_t HO, int64_t WO, int64_t act,
+                        int64_t stride);
 torch::Tensor panel_gather(torch::Tensor src, torch::Tensor ktab);
-torch::Tensor conv_wrw(torch::Tensor xbuf, torch::Tensor dy,
-                       torch::Tensor mbase, torch::Tensor koff, int64_t N,
-                       int64_t K, int64_t WO, bool mcontig, int64_t vm,
-                       int64_t st, int64_t vpt, int64_t vpl, int64_t vsv);
+torch::Tensor conv_wrw_gather(torch::Tensor x, torch::Tensor dy,
+                              torch::Tensor mpack, torch::Tensor kpack,
+                              int64_t N, int64_t K, int64_t WO, int64_t st,
+                              int64_t pt, int64_t pl);
+torch::Tensor conv_wrw_flat(torch::Tensor xbuf, torch::Tensor dy,
+                            torch::Tensor mbase, torch::Tensor koff, int64_t N,
+                            int64_t K, int64_t WO, bool mcontig);
 torch::Tensor act_bwd(torch::Tensor dy, torch::Tensor y, int64_t act);
 torch::Tensor wmat_make(torch::Tensor w1, int64_t khw, int64_t mode);
 void adam_step(torch::Tensor p, torch::Tensor g, torch::Tensor m,
@@ -110,8 +127,42 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_tables", &dsin::conv_tables, "gather-conv offset tables");
   m.def("conv_tables_v2", &dsin::conv_tables_v2,
         "packed-coordinate tables for the virtual-pad gather path");
-  m.def("conv_fwd", &dsin::conv_fwd, "implicit-GEMM gather conv forward");
-  m.def("conv_wrw", &dsin::conv_wrw, "implicit-GEMM conv weight gradient");
+  // Implicit-GEMM conv family. N = output channels, K = taps (Cin*kh*kw);
+  // the two *_variant functions are the launch code's own selection and
+  // touch no device, so they answer on a machine without a GPU.
+  m.def("conv_fwd_variant", &dsin::conv_fwd_variant,
+        "(TM, VM, VST, VSV, run-time stride) of one forward gather launch",
+        py::arg("B"), py::arg("M"), py::arg("N"), py::arg("WO"),
+        py::arg("st"), py::arg("sv"), py::arg("flat"));
+  m.def("conv_wrw_variant", &dsin::conv_wrw_variant,
+        "(VM, VST) of one weight-gradient launch", py::arg("WO"),
+        py::arg("st"), py::arg("flat"));
+  m.def("conv_direct", &dsin::conv_direct,
+        "direct LDS-halo conv: ksize 3 (stride 1) or 5 (stride 2)",
+        py::arg("x"), py::arg("wmat"), py::arg("bias"), py::arg("N"),
+        py::arg("HO"), py::arg("WO"), py::arg("act"), py::arg("vpad"),
+        py::arg("ksize"));
+  m.def("conv_gather", &dsin::conv_gather,
+        "virtual-pad gather conv; with out, a phase written strided into it",
+        py::arg("x"), py::arg("wmat"), py::arg("bias"), py::arg("mpack"),
+        py::arg("kpack"), py::arg("N"), py::arg("K"), py::arg("HO"),
+        py::arg("WO"), py::arg("act"), py::arg("st"), py::arg("sv"),
+        py::arg("pt"), py::arg("pl"), py::arg("out") = py::none(),
+        py::arg("oh0") = 0, py::arg("ow0") = 0, py::arg("ostep") = 1);
+  m.def("conv_flat", &dsin::conv_flat,
+        "gather conv over a pre-padded buffer, flat tables (bf16 or e4m3)",
+        py::arg("xbuf"), py::arg("wmat"), py::arg("bias"), py::arg("mbase"),
+        py::arg("koff"), py::arg("N"), py::arg("K"), py::arg("HO"),
+        py::arg("WO"), py::arg("act"), py::arg("stride"));
+  m.def("conv_wrw_gather", &dsin::conv_wrw_gather,
+        "weight gradient of conv_gather (sv = 1)", py::arg("x"),
+        py::arg("dy"), py::arg("mpack"), py::arg("kpack"), py::arg("N"),
+        py::arg("K"), py::arg("WO"), py::arg("st"), py::arg("pt"),
+        py::arg("pl"));
+  m.def("conv_wrw_flat", &dsin::conv_wrw_flat,
+        "weight gradient of conv_flat", py::arg("xbuf"), py::arg("dy"),
+        py::arg("mbase"), py::arg("koff"), py::arg("N"), py::arg("K"),
+        py::arg("WO"), py::arg("mcontig"));
   m.def("act_bwd", &dsin::act_bwd, "fused activation gradient (bf16 out)");
   m.def("wmat_make", &dsin::wmat_make, "padded/rotated bf16 conv W panel");
   m.def("panel_gather", &dsin::panel_gather,

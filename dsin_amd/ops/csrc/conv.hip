@@ -38,87 +38,112 @@ std::tuple<torch::Tensor, torch::Tensor> conv_tables_v2(
   return {mpack, kpack};
 }
 
-torch::Tensor conv_fwd(torch::Tensor xbuf, torch::Tensor wmat,
-                       c10::optional<torch::Tensor> bias,
-                       torch::Tensor mbase, torch::Tensor koff, int64_t N,
-                       int64_t K, int64_t HO, int64_t WO, int64_t act,
-                       int64_t stride, int64_t direct, int64_t vpad,
-                       int64_t vm, int64_t vpt, int64_t vpl, int64_t vsv,
-                       c10::optional<torch::Tensor> out_opt, int64_t oh0,
-                       int64_t ow0, int64_t ostep, int64_t wof) {
-  CHECK_CUDA_CONTIG(xbuf);
-  CHECK_CUDA_CONTIG(wmat);
-  const bool fp8 = xbuf.scalar_type() == torch::kByte;  // raw e4m3 bytes
-  TORCH_CHECK(fp8 || xbuf.scalar_type() == torch::kBFloat16,
-              "xbuf must be bf16 or e4m3-as-uint8");
-  TORCH_CHECK(wmat.scalar_type() == xbuf.scalar_type(), "x/w dtype mismatch");
-  const int64_t B = xbuf.size(0);
-  const int64_t M = HO * WO;
-  if (direct == 2 && !fp8) {
-    // 5x5 stride-2 direct LDS-halo kernel (virtual pad)
-    const int64_t Ci = xbuf.size(1);
-    const int64_t KPd = (K + 63) & ~63;
-    TORCH_CHECK(K == Ci * 25 && Ci % 64 == 0 && stride == 2,
-                "direct5 conv gate mismatch");
-    TORCH_CHECK(wmat.size(1) == KPd + CONV_AP, "direct5 wmat stride mismatch");
-    const int Hp = (int)xbuf.size(2), Wp = (int)xbuf.size(3);
-    TORCH_CHECK(HO == (Hp + 2 * vpad - 5) / 2 + 1 &&
-                    WO == (Wp + 2 * vpad - 5) / 2 + 1,
-                "direct5 conv size mismatch");
-    auto out = torch::empty({B, N, HO, WO},
-                            xbuf.options().dtype(torch::kBFloat16));
-    const float* bp = nullptr;
-    if (bias.has_value()) {
-      CHECK_CUDA_CONTIG(bias.value());
-      bp = bias->data_ptr<float>();
-    }
-    dim3 grid(((HO + 7) / 8) * ((WO + 7) / 8), (N + 63) / 64, B);
-    size_t lds = (size_t)19 * 19 * 64 * 2;
-    hipLaunchKernelGGL(conv5x5s2_direct_kernel, grid, dim3(256), lds,
-                       at::cuda::getCurrentCUDAStream(),
-                       (const cvbf16*)xbuf.data_ptr(),
-                       (const cvbf16*)wmat.data_ptr(), bp,
-                       (cvbf16*)out.data_ptr(), (int)Ci, Hp, Wp, (int)N,
-                       (int)HO, (int)WO, (int)KPd, xbuf.stride(0),
-                       (long long)N * M, (int)act, (int)vpad);
-    return out;
-  }
-  if (direct && !fp8) {
-    // stride-1 3x3, Ci%64==0: direct LDS-halo kernel (9x less gather
-    // traffic than the im2col path); caller built wmat in mode-2/3 layout
-    const int64_t Ci = xbuf.size(1);
-    const int64_t KPd = (K + 63) & ~63;
-    TORCH_CHECK(K == Ci * 9 && Ci % 64 == 0 && stride == 1,
-                "direct conv gate mismatch");
-    TORCH_CHECK(wmat.size(1) == KPd + CONV_AP, "direct wmat stride mismatch");
-    auto out = torch::empty({B, N, HO, WO},
-                            xbuf.options().dtype(torch::kBFloat16));
-    const float* bp = nullptr;
-    if (bias.has_value()) {
-      CHECK_CUDA_CONTIG(bias.value());
-      bp = bias->data_ptr<float>();
-    }
-    const int Hp = (int)xbuf.size(2), Wp = (int)xbuf.size(3);
-    TORCH_CHECK(HO == Hp + 2 * vpad - 2 && WO == Wp + 2 * vpad - 2,
-                "direct conv size mismatch");
-    dim3 grid(((HO + 7) / 8) * ((WO + 7) / 8), (N + 63) / 64, B);
-    size_t lds = (size_t)2 * 10 * 11 * 64 * 2;
-    hipLaunchKernelGGL(conv3x3_direct_kernel, grid, dim3(256), lds,
-                       at::cuda::getCurrentCUDAStream(),
-                       (const cvbf16*)xbuf.data_ptr(),
-                       (const cvbf16*)wmat.data_ptr(), bp,
-                       (cvbf16*)out.data_ptr(), (int)Ci, Hp, Wp, (int)N,
-                       (int)HO, (int)WO, (int)KPd, xbuf.stride(0),
-                       (long long)N * M, (int)act, (int)vpad);
-    return out;
-  }
+// Which instantiation runs is decided by the two functions below: pure host
+// arithmetic (no HIP call, no device tensor), bound to Python as well, so
+// the tests ask the very functions the launch code asks. Forward: B images
+// of M pixels x N channels, WO pixels per output row, conv stride st on an
+// input stuffed by sv; flat = flat-offset tables over a pre-padded buffer.
+// Returns (TM, VM, VST, VSV) and the run-time stride handed to the kernel.
+std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t> conv_fwd_variant(
+    int64_t B, int64_t M, int64_t N, int64_t WO, int64_t st, int64_t sv,
+    bool flat) {
+  if (WO < 8) st = 0;  // generic per-element staging for very narrow outputs
+  // TM=64 is the throughput tile; when its grid would underfill 256 CUs
+  // (< ~3 workgroups/CU) halve the pixel tile to double parallelism — the
+  // small-M resblock convs (40x120) are latency-bound, not FLOP-bound.
+  const int64_t wgs64 =
+      ((M + CONV_TM - 1) / CONV_TM) * ((N + CONV_TN - 1) / CONV_TN) * B;
+  const int64_t TM = (wgs64 < 256 && M > CONV_TM) ? 32 : 64;
+  if (flat) return {TM, 0, 0, 1, st};
+  if (sv > 2) return {TM, 1, 0, 0, st};  // stuff stride taken at run time
+  if (sv == 2) return {TM, 1, st == 1 ? 1 : 0, 2, st};
+  return {TM, 1, (st == 1 || st == 2) ? st : 0, 1, st};
+}
+
+// (VM, VST) of one weight-gradient launch.
+std::tuple<int64_t, int64_t> conv_wrw_variant(int64_t WO, int64_t st,
+                                              bool flat) {
+  if (flat) return {0, 0};
+  return {1, (WO < 8 || (st != 1 && st != 2)) ? 0 : st};
+}
+
+// the instantiations, each written once
+using FwdKern = decltype(&conv_fwd_kernel<64, 0, 0, 1>);
+struct FwdEntry { int VM, VST, VSV; FwdKern tm64, tm32; };
+template <int VM, int VST, int VSV>
+constexpr FwdEntry fwd_entry() {
+  return {VM, VST, VSV, conv_fwd_kernel<64, VM, VST, VSV>,
+          conv_fwd_kernel<32, VM, VST, VSV>};
+}
+static const FwdEntry FWD_TABLE[] = {
+    fwd_entry<0, 0, 1>(), fwd_entry<1, 1, 1>(), fwd_entry<1, 2, 1>(),
+    fwd_entry<1, 0, 1>(), fwd_entry<1, 1, 2>(), fwd_entry<1, 0, 2>(),
+    fwd_entry<1, 0, 0>()};
+
+static const decltype(&conv_wrw_kernel<0, 0>) WRW_TABLE[2][3] = {  // [VM][VST]
+    {conv_wrw_kernel<0, 0>, nullptr, nullptr},
+    {conv_wrw_kernel<1, 0>, conv_wrw_kernel<1, 1>, conv_wrw_kernel<1, 2>}};
+
+static void check_operands(const torch::Tensor& x, const torch::Tensor& w,
+                           bool fp8_ok) {
+  CHECK_CUDA_CONTIG(x);
+  CHECK_CUDA_CONTIG(w);
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 ||
+                  (fp8_ok && x.scalar_type() == torch::kByte),
+              "x must be bf16 (flat tables: or e4m3-as-uint8)");
+  TORCH_CHECK(w.scalar_type() == x.scalar_type(), "x/w dtype mismatch");
+}
+
+static const float* bias_ptr(const c10::optional<torch::Tensor>& bias) {
+  if (!bias.has_value()) return nullptr;
+  CHECK_CUDA_CONTIG(bias.value());
+  return bias->data_ptr<float>();
+}
+
+// Direct LDS-halo kernels (virtual pad vpad; wmat in the mode-2/3 layout of
+// wmat_make): ksize 3 is the stride-1 3x3, ksize 5 the stride-2 5x5.
+torch::Tensor conv_direct(torch::Tensor x, torch::Tensor wmat,
+                          c10::optional<torch::Tensor> bias, int64_t N,
+                          int64_t HO, int64_t WO, int64_t act, int64_t vpad,
+                          int64_t ksize) {
+  check_operands(x, wmat, false);
+  const int64_t stride = ksize == 3 ? 1 : 2;
+  const int64_t B = x.size(0), Ci = x.size(1), Hp = x.size(2), Wp = x.size(3);
+  const int64_t KPd = (Ci * ksize * ksize + 63) & ~63;
+  TORCH_CHECK((ksize == 3 || ksize == 5) && Ci % 64 == 0,
+              "direct conv gate mismatch: ksize 3 or 5, Ci % 64 == 0");
+  TORCH_CHECK(wmat.size(1) == KPd + CONV_AP, "direct wmat stride mismatch");
+  TORCH_CHECK(HO == (Hp + 2 * vpad - ksize) / stride + 1 &&
+                  WO == (Wp + 2 * vpad - ksize) / stride + 1,
+              "direct conv size mismatch");
+  auto out = torch::empty({B, N, HO, WO}, x.options());
+  dim3 grid(((HO + 7) / 8) * ((WO + 7) / 8), (N + 63) / 64, B);
+  const size_t lds = ksize == 3 ? (size_t)2 * 10 * 11 * 64 * 2
+                                : (size_t)19 * 19 * 64 * 2;
+  hipLaunchKernelGGL(
+      ksize == 3 ? conv3x3_direct_kernel : conv5x5s2_direct_kernel, grid,
+      dim3(256), lds, at::cuda::getCurrentCUDAStream(),
+      (const cvbf16*)x.data_ptr(), (const cvbf16*)wmat.data_ptr(),
+      bias_ptr(bias), (cvbf16*)out.data_ptr(), (int)Ci, (int)Hp, (int)Wp,
+      (int)N, (int)HO, (int)WO, (int)KPd, x.stride(0),
+      (long long)N * HO * WO, (int)act, (int)vpad);
+  return out;
+}
+
+// The gather-GEMM launch behind conv_gather and conv_flat (fp8 is flat).
+static torch::Tensor gather_launch(
+    torch::Tensor x, torch::Tensor wmat, c10::optional<torch::Tensor> bias,
+    torch::Tensor mtab, torch::Tensor ktab, int64_t N, int64_t K, int64_t HO,
+    int64_t WO, int64_t act, int64_t st, int64_t sv, int64_t pt, int64_t pl,
+    bool flat, c10::optional<torch::Tensor> out_opt, int64_t oh0, int64_t ow0,
+    int64_t ostep) {
+  check_operands(x, wmat, flat);
+  const int64_t B = x.size(0), M = HO * WO;
   const int64_t KP = (K + 63) & ~63;  // 64-chunk padded; wmat zero-padded
   TORCH_CHECK(wmat.size(1) == KP + CONV_AP, "wmat row stride mismatch");
-  if (WO < 8) stride = 0;  // scalar staging path for very narrow outputs
   // phase-strided output: write into a caller-provided full-grid tensor
   torch::Tensor out;
-  long long o_chan = M, o_img = (long long)N * M;
-  int WOf = (int)WO;
+  long long o_chan = M, WOf = WO;  // channel stride and row width of `out`
   if (out_opt.has_value()) {
     out = out_opt.value();
     CHECK_CUDA_CONTIG(out);
@@ -126,155 +151,129 @@ torch::Tensor conv_fwd(torch::Tensor xbuf, torch::Tensor wmat,
                     out.size(0) == B && out.size(1) == N,
                 "phase out tensor mismatch");
     o_chan = (long long)out.size(2) * out.size(3);
-    o_img = (long long)N * o_chan;
-    WOf = (int)out.size(3);
+    WOf = out.size(3);
   } else {
     TORCH_CHECK(ostep == 1, "strided output needs an out tensor");
     out = torch::empty({B, N, HO, WO},
-                       xbuf.options().dtype(torch::kBFloat16));
+                       x.options().dtype(torch::kBFloat16));
   }
-  const float* bptr = nullptr;
-  if (bias.has_value()) {
-    CHECK_CUDA_CONTIG(bias.value());
-    bptr = bias->data_ptr<float>();
-  }
-  dim3 grid((M + CONV_TM - 1) / CONV_TM, (N + CONV_TN - 1) / CONV_TN, B);
-  if (fp8) {
-    TORCH_CHECK(!out_opt.has_value(), "fp8 path has no phase output");
-    size_t lds = (size_t)2 * CONV8_TM * (64 + CONV8_AP);
-    hipLaunchKernelGGL(conv_fwd_fp8_kernel, grid, dim3(256), lds,
+  if (x.scalar_type() == torch::kByte) {
+    dim3 grid((M + CONV_TM - 1) / CONV_TM, (N + CONV_TN - 1) / CONV_TN, B);
+    hipLaunchKernelGGL(conv_fwd_fp8_kernel, grid, dim3(256),
+                       (size_t)2 * CONV8_TM * (64 + CONV8_AP),
                        at::cuda::getCurrentCUDAStream(),
-                       (const f8*)xbuf.data_ptr(), (const f8*)wmat.data_ptr(),
-                       bptr, (cvbf16*)out.data_ptr(), mbase.data_ptr<int>(),
-                       koff.data_ptr<int>(), (int)M, (int)N, (int)K, (int)KP,
-                       xbuf.stride(0), (long long)N * M, (int)act, (int)WO,
-                       (int)stride);
+                       (const f8*)x.data_ptr(), (const f8*)wmat.data_ptr(),
+                       bias_ptr(bias), (cvbf16*)out.data_ptr(),
+                       mtab.data_ptr<int>(), ktab.data_ptr<int>(), (int)M,
+                       (int)N, (int)K, (int)KP, x.stride(0), (long long)N * M,
+                       (int)act, (int)WO, (int)(WO < 8 ? 0 : st));
     return out;
   }
-  // TM=64 is the throughput tile; when its grid would underfill 256 CUs
-  // (< ~3 workgroups/CU) halve the pixel tile to double parallelism — the
-  // small-M resblock convs (40x120) are latency-bound, not FLOP-bound.
-  const int vH = (int)xbuf.size(2), vW = (int)xbuf.size(3);
-  using FwdKern = void (*)(const cvbf16*, const cvbf16*, const float*,
-                           cvbf16*, const int*, const int*, int, int, int,
-                           int, long long, long long, int, int, int, int,
-                           int, int, int, int, int, int, int, int,
-                           long long);
-  auto pick_fwd = [&](bool tm32) -> FwdKern {
-    if (!vm) return tm32 ? conv_fwd_kernel<32, 0, 0, 1>
-                         : conv_fwd_kernel<64, 0, 0, 1>;
-    // compile-time (stride, stuff) specialization for the virtual path
-    if (vsv > 2)  // backward-data of a stride >= 3 conv: run-time stuffing
-      return tm32 ? conv_fwd_kernel<32, 1, 0, 0> : conv_fwd_kernel<64, 1, 0, 0>;
-    if (vsv == 2) {
-      if (stride == 1)
-        return tm32 ? conv_fwd_kernel<32, 1, 1, 2>
-                    : conv_fwd_kernel<64, 1, 1, 2>;
-      return tm32 ? conv_fwd_kernel<32, 1, 0, 2>
-                  : conv_fwd_kernel<64, 1, 0, 2>;
-    }
-    if (stride == 1)
-      return tm32 ? conv_fwd_kernel<32, 1, 1, 1>
-                  : conv_fwd_kernel<64, 1, 1, 1>;
-    if (stride == 2)
-      return tm32 ? conv_fwd_kernel<32, 1, 2, 1>
-                  : conv_fwd_kernel<64, 1, 2, 1>;
-    return tm32 ? conv_fwd_kernel<32, 1, 0, 1> : conv_fwd_kernel<64, 1, 0, 1>;
-  };
-  const long long wgs64 = (long long)grid.x * grid.y * grid.z;
-  if (wgs64 < 256 && M > CONV_TM) {
-    dim3 grid32((M + 31) / 32, grid.y, grid.z);
-    size_t lds32 = (size_t)4 * 32 * (64 + CONV_AP) * 2;
-    hipLaunchKernelGGL(pick_fwd(true), grid32, dim3(256), lds32,
-                       at::cuda::getCurrentCUDAStream(),
-                       (const cvbf16*)xbuf.data_ptr(),
-                       (const cvbf16*)wmat.data_ptr(), bptr,
-                       (cvbf16*)out.data_ptr(), mbase.data_ptr<int>(),
-                       koff.data_ptr<int>(), (int)M, (int)N, (int)K, (int)KP,
-                       xbuf.stride(0), o_img, (int)act, (int)WO,
-                       (int)stride, vH, vW, (int)vpt, (int)vpl, (int)vsv,
-                       (int)oh0, (int)ow0, (int)ostep, WOf, o_chan);
-    return out;
-  }
-  size_t lds = (size_t)4 * CONV_TM * (64 + CONV_AP) * 2;  // 4-buffer pipeline
-  hipLaunchKernelGGL(pick_fwd(false), grid, dim3(256), lds,
+  const auto [TM, VM, VST, VSV, kstride] =
+      conv_fwd_variant(B, M, N, WO, st, sv, flat);
+  FwdKern kern = nullptr;
+  for (const FwdEntry& e : FWD_TABLE)
+    if (e.VM == VM && e.VST == VST && e.VSV == VSV)
+      kern = TM == 32 ? e.tm32 : e.tm64;
+  TORCH_CHECK(kern != nullptr, "no conv_fwd_kernel instantiation");
+  dim3 grid((M + TM - 1) / TM, (N + CONV_TN - 1) / CONV_TN, B);
+  const size_t lds = (size_t)4 * TM * (64 + CONV_AP) * 2;  // 4-buffer pipeline
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds,
                      at::cuda::getCurrentCUDAStream(),
-                     (const cvbf16*)xbuf.data_ptr(),
-                     (const cvbf16*)wmat.data_ptr(), bptr,
-                     (cvbf16*)out.data_ptr(), mbase.data_ptr<int>(),
-                     koff.data_ptr<int>(), (int)M, (int)N, (int)K, (int)KP,
-                     xbuf.stride(0), o_img, (int)act, (int)WO,
-                     (int)stride, vH, vW, (int)vpt, (int)vpl, (int)vsv,
-                     (int)oh0, (int)ow0, (int)ostep, WOf, o_chan);
+                     (const cvbf16*)x.data_ptr(),
+                     (const cvbf16*)wmat.data_ptr(), bias_ptr(bias),
+                     (cvbf16*)out.data_ptr(), mtab.data_ptr<int>(),
+                     ktab.data_ptr<int>(), (int)M, (int)N, (int)K, (int)KP,
+                     x.stride(0), (long long)N * o_chan, (int)act, (int)WO,
+                     (int)kstride, (int)x.size(2), (int)x.size(3), (int)pt,
+                     (int)pl, (int)sv, (int)oh0, (int)ow0, (int)ostep,
+                     (int)WOf, o_chan);
   return out;
 }
 
-torch::Tensor conv_wrw(torch::Tensor xbuf, torch::Tensor dy,
-                       torch::Tensor mbase, torch::Tensor koff, int64_t N,
-                       int64_t K, int64_t WO, bool mcontig, int64_t vm,
-                       int64_t st, int64_t vpt, int64_t vpl, int64_t vsv) {
-  CHECK_CUDA_CONTIG(xbuf);
-  CHECK_CUDA_CONTIG(dy);
-  const bool fp8 = xbuf.scalar_type() == torch::kByte;
-  const int64_t B = xbuf.size(0);
-  const int64_t M = dy.size(2) * dy.size(3);
+// Packed tables on the raw x, virtual pad (pt, pl) and stuffing sv. With
+// `out`, pixel (h, w) lands at (oh0 + ostep*h, ow0 + ostep*w) of it (phases).
+torch::Tensor conv_gather(torch::Tensor x, torch::Tensor wmat,
+                          c10::optional<torch::Tensor> bias,
+                          torch::Tensor mpack, torch::Tensor kpack, int64_t N,
+                          int64_t K, int64_t HO, int64_t WO, int64_t act,
+                          int64_t st, int64_t sv, int64_t pt, int64_t pl,
+                          c10::optional<torch::Tensor> out, int64_t oh0,
+                          int64_t ow0, int64_t ostep) {
+  TORCH_CHECK(sv >= 1, "conv_gather: stuff stride sv must be >= 1");
+  return gather_launch(x, wmat, bias, mpack, kpack, N, K, HO, WO, act, st, sv,
+                       pt, pl, false, out, oh0, ow0, ostep);
+}
+
+// Flat-offset tables over a pre-padded buffer: bf16 (conv3d) or e4m3.
+torch::Tensor conv_flat(torch::Tensor xbuf, torch::Tensor wmat,
+                        c10::optional<torch::Tensor> bias,
+                        torch::Tensor mbase, torch::Tensor koff, int64_t N,
+                        int64_t K, int64_t HO, int64_t WO, int64_t act,
+                        int64_t stride) {
+  return gather_launch(xbuf, wmat, bias, mbase, koff, N, K, HO, WO, act,
+                       stride, 1, 0, 0, true, c10::nullopt, 0, 0, 1);
+}
+
+// Weight gradient behind conv_wrw_gather and conv_wrw_flat (fp8 is flat).
+static torch::Tensor wrw_launch(torch::Tensor x, torch::Tensor dy,
+                                torch::Tensor mtab, torch::Tensor ktab,
+                                int64_t N, int64_t K, int64_t WO,
+                                bool mcontig, int64_t st, int64_t pt,
+                                int64_t pl, bool flat) {
+  check_operands(x, dy, flat);
+  const int64_t B = x.size(0), M = dy.size(2) * dy.size(3);
   // pick pixel chunking so the grid fills the chip (~6 workgroups/CU).
   // Each (tap-tile, cout-tile, chunk) workgroup owns a disjoint 64x64 region
   // of its chunk's PARTIAL-SUM slice — plain stores, no atomics (atomicAdd
   // across ~40 chunks contends on the same dw cache lines and was measured
-  // slower than the 9-chunk version it replaced). The slices are then
-  // reduced with one sum(0). Total partial memory is bounded by the
-  // workgroup target: <= 1536 * 64*64*4B = 25 MB.
+  // slower). The slices are then reduced with one sum(0); their memory is
+  // bounded by the workgroup target: <= 1536 * 64*64*4B = 25 MB.
   const int64_t tiles = ((K + 63) / 64) * ((N + 63) / 64) * B;
   int pix_chunks = (int)std::min<int64_t>(
       std::max<int64_t>(1536 / std::max<int64_t>(tiles, 1), 1),
       std::max<int64_t>(M / 256, 1));
-  // every in-range (cout, tap) element of every slice is written exactly
-  // once by its owning workgroup, so empty() needs no zero-fill.
+  // every in-range element of every slice is written once: no zero-fill
   auto dwp = torch::empty({(int64_t)B * pix_chunks, N, K},
-                          xbuf.options().dtype(torch::kFloat32));
+                          x.options().dtype(torch::kFloat32));
   dim3 grid((K + 63) / 64, (N + 63) / 64, B * pix_chunks);
-  if (fp8) {
-    TORCH_CHECK(dy.scalar_type() == torch::kByte, "fp8 wrw: dy must be e4m3");
-    size_t lds = (size_t)4 * 64 * (32 + CONV8_AP);
-    hipLaunchKernelGGL(conv_wrw_fp8_kernel, grid, dim3(256), lds,
+  if (x.scalar_type() == torch::kByte) {
+    hipLaunchKernelGGL(conv_wrw_fp8_kernel, grid, dim3(256),
+                       (size_t)4 * 64 * (32 + CONV8_AP),
                        at::cuda::getCurrentCUDAStream(),
-                       (const f8*)xbuf.data_ptr(), (const f8*)dy.data_ptr(),
-                       dwp.data_ptr<float>(), mbase.data_ptr<int>(),
-                       koff.data_ptr<int>(), (int)M, (int)N, (int)K,
-                       xbuf.stride(0), dy.stride(0), pix_chunks, (int)WO,
-                       (int)(mcontig ? 1 : 0));
+                       (const f8*)x.data_ptr(), (const f8*)dy.data_ptr(),
+                       dwp.data_ptr<float>(), mtab.data_ptr<int>(),
+                       ktab.data_ptr<int>(), (int)M, (int)N, (int)K,
+                       x.stride(0), dy.stride(0), pix_chunks, (int)WO,
+                       (int)mcontig);
   } else {
+    const auto [VM, VST] = conv_wrw_variant(WO, st, flat);
     size_t lds = (size_t)4 * 64 * (32 + CONV_AP) * 2;  // 2 tiles x dbuf
-    const int vH = (int)xbuf.size(2), vW = (int)xbuf.size(3);
-    using WrwKern = void (*)(const cvbf16*, const cvbf16*, float*,
-                             const int*, const int*, int, int, int,
-                             long long, long long, int, int, int, int, int,
-                             int, int, int, int);
-    WrwKern kern;
-    if (!vm) {
-      kern = conv_wrw_kernel<0, 0, 1>;
-    } else {
-      const bool gen = (WO < 8) || (st != 1 && st != 2);
-      if (vsv == 2)
-        kern = (!gen && st == 1) ? conv_wrw_kernel<1, 1, 2>
-                                 : conv_wrw_kernel<1, 0, 2>;
-      else if (gen)
-        kern = conv_wrw_kernel<1, 0, 1>;
-      else
-        kern = (st == 1) ? conv_wrw_kernel<1, 1, 1> : conv_wrw_kernel<1, 2, 1>;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds,
+    hipLaunchKernelGGL(WRW_TABLE[VM][VST], grid, dim3(256), lds,
                        at::cuda::getCurrentCUDAStream(),
-                       (const cvbf16*)xbuf.data_ptr(),
+                       (const cvbf16*)x.data_ptr(),
                        (const cvbf16*)dy.data_ptr(), dwp.data_ptr<float>(),
-                       mbase.data_ptr<int>(), koff.data_ptr<int>(), (int)M,
-                       (int)N, (int)K, xbuf.stride(0), dy.stride(0),
-                       pix_chunks, (int)WO, (int)(mcontig ? 1 : 0), (int)st,
-                       vH, vW, (int)vpt, (int)vpl, (int)vsv);
+                       mtab.data_ptr<int>(), ktab.data_ptr<int>(), (int)M,
+                       (int)N, (int)K, x.stride(0), dy.stride(0), pix_chunks,
+                       (int)WO, (int)mcontig, (int)st, (int)x.size(2),
+                       (int)x.size(3), (int)pt, (int)pl);
   }
   if (B * pix_chunks == 1) return dwp.view({N, K});
   return dwp.sum(0);
+}
+
+torch::Tensor conv_wrw_gather(torch::Tensor x, torch::Tensor dy,
+                              torch::Tensor mpack, torch::Tensor kpack,
+                              int64_t N, int64_t K, int64_t WO, int64_t st,
+                              int64_t pt, int64_t pl) {
+  return wrw_launch(x, dy, mpack, kpack, N, K, WO, false, st, pt, pl, false);
+}
+
+// mcontig: 8 pixels of an output row are contiguous in xbuf (flat staging only)
+torch::Tensor conv_wrw_flat(torch::Tensor xbuf, torch::Tensor dy,
+                            torch::Tensor mbase, torch::Tensor koff, int64_t N,
+                            int64_t K, int64_t WO, bool mcontig) {
+  return wrw_launch(xbuf, dy, mbase, koff, N, K, WO, mcontig, 1, 0, 0, true);
 }
 
 torch::Tensor panel_gather(torch::Tensor src, torch::Tensor ktab) {

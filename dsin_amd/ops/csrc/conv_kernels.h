@@ -2,12 +2,17 @@
 //
 // One gather-GEMM forward kernel covers every 2D conv shape in DSIN
 // (SURVEY.md section 2b, K1-K3, K15): direct conv with any stride/dilation,
-// transposed conv (host zero-stuffs the input), and backward-data (host
+// transposed conv (the zero-stuffed input exists only virtually, or the
+// host splits it into four dense phase sub-convs), and backward-data (host
 // passes spatially-rotated ci<->co-swapped weights) — the geometry lives in
-// two per-shape offset tables, not in the kernel:
-//   mbase[m] = input-pixel base offset of output pixel m in the PADDED image
-//   koff[k]  = offset of filter tap k = (ci, r, s) in the padded image
-// so A[m][k] = xpad[mbase[m] + koff[k]] and the conv is the GEMM
+// two per-shape tables, not in the kernel. Packed coordinates (VM=1, every
+// 2D conv) on the RAW tensor, pad ring and stuff holes staged as zeros:
+//   mpack[m] = oh*st << 16 | ow*st        of output pixel m
+//   kpack[k] = ci << 20 | r*dil << 10 | s*dil   of tap k = (ci, r, s)
+// or flat offsets (VM=0, conv3d and the fp8 twins) into a PRE-PADDED buffer:
+//   mbase[m] = input-pixel base offset of output pixel m in the padded image
+//   koff[k]  = offset of filter tap k in the padded image
+// so A[m][k] = xpad[mbase[m] + koff[k]]. Either way the conv is the GEMM
 //   out[M=pixels][N=couts] = A @ W^T,  W as [co][K] (the natural torch
 //   weight layout flattened), bf16 MFMA 16x16x32, fp32 accumulate.
 //
@@ -860,7 +865,7 @@ void conv5x5s2_direct_kernel(const cvbf16* __restrict__ xpad, // (Ci, Hp, Wp)
 // dW[co][k] += sum over the workgroup's pixel chunk of dy[co][m]*A[m][k].
 // GEMM roles: A' (M'=filter taps K) gathered rows, B' = dy columns.
 // Tile: M'64 (taps) x N'64 (couts), K' = pixels chunked by 32.
-template <int VM, int VST, int VSV>
+template <int VM, int VST>
 __global__ __launch_bounds__(256)
 void conv_wrw_kernel(const cvbf16* __restrict__ xpad,  // (Ci, Hp, Wp)
                      const cvbf16* __restrict__ dy,    // (Co, M)
@@ -870,7 +875,7 @@ void conv_wrw_kernel(const cvbf16* __restrict__ xpad,  // (Ci, Hp, Wp)
                      int M, int N, int K,
                      long long x_img_stride, long long dy_img_stride,
                      int pix_chunks, int WO, int mcontig,
-                     int st, int vH, int vW, int vpt, int vpl, int vsv) {
+                     int st, int vH, int vW, int vpt, int vpl) {
   // blockIdx.x: tap tile; blockIdx.y: cout tile; blockIdx.z: pixel chunk*img
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int ASTR = 32 + CONV_AP;
@@ -928,11 +933,11 @@ void conv_wrw_kernel(const cvbf16* __restrict__ xpad,  // (Ci, Hp, Wp)
           // ow is recoverable from the packed field (= ow*VST): no int div
           const int cross = WO - ((mpA & 0xffff) >> (VST == 2 ? 1 : 0));
           cv_u16x8 va, vb;
-          vstage8<VST ? VST : 1, VSV>(x, vH, vW, kci, hA, wA, va);
+          vstage8<VST ? VST : 1, 1>(x, vH, vW, kci, hA, wA, va);
           if (__any(cross < 8)) {
             const int hB = (mpB >> 16) + kdh - vpt;
             const int wB = (mpB & 0xffff) - 7 * VST + kdw - vpl;
-            vstage8<VST ? VST : 1, VSV>(x, vH, vW, kci, hB, wB, vb);
+            vstage8<VST ? VST : 1, 1>(x, vH, vW, kci, hB, wB, vb);
 #pragma unroll
             for (int i = 0; i < 8; ++i)
               sa[i] = (p + i < p1) ? ((i < cross) ? va[i] : vb[i])
@@ -948,19 +953,11 @@ void conv_wrw_kernel(const cvbf16* __restrict__ xpad,  // (Ci, Hp, Wp)
             const int mp = mbase[min(p + i, M - 1)];
             const int hv = (mp >> 16) + kdh - vpt;
             const int wv = (mp & 0xffff) + kdw - vpl;
-            bool ok = p + i < p1;
-            long long a;
-            if (VSV == 2) {
-              ok = ok && hv >= 0 && !(hv & 1) && (hv >> 1) < vH && wv >= 0 &&
-                   !(wv & 1) && (wv >> 1) < vW;
-              a = ((long long)kci * vH + min(max(hv >> 1, 0), vH - 1)) * vW +
-                  min(max(wv >> 1, 0), vW - 1);
-            } else {
-              ok = ok && (unsigned)hv < (unsigned)vH &&
-                   (unsigned)wv < (unsigned)vW;
-              a = ((long long)kci * vH + min(max(hv, 0), vH - 1)) * vW +
-                  min(max(wv, 0), vW - 1);
-            }
+            const bool ok = p + i < p1 && (unsigned)hv < (unsigned)vH &&
+                            (unsigned)wv < (unsigned)vW;
+            const long long a =
+                ((long long)kci * vH + min(max(hv, 0), vH - 1)) * vW +
+                min(max(wv, 0), vW - 1);
             const cvbf16 v = x[a];
             sa[i] = ok ? *reinterpret_cast<const unsigned short*>(&v)
                        : (unsigned short)0;

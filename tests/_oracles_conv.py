@@ -23,7 +23,10 @@ K steps, 2 the bias add and the leaky multiply; the factor 2 allows the
 matrix unit's internal additions to truncate. KP is what the launch really
 uses: the 64-padded K of a gather launch, a phase's own Kp padded to 64,
 Ci*khw for the direct kernels. plan() mirrors the host-side selection of
-ops/conv.py and csrc/conv.hip to find it.
+ops/conv.py (_route, _gather) and csrc/conv.hip (conv_fwd_variant,
+conv_wrw_variant) to find it; the mirror stays independent Python, and
+tests/test_conv_oracle.py compares it with the code it mirrors for every
+launch of every case.
 """
 
 import functools
@@ -186,8 +189,9 @@ def out_size(c):
 
 
 def wrw_chunks(B, M, K, Co):
-    """(pix_chunks, PCHUNK, [p0 of every slice]) of one conv_wrw launch: the
-    host formula of csrc/conv.hip and the kernel's own slice start."""
+    """(pix_chunks, PCHUNK, [p0 of every slice]) of one weight-gradient
+    launch: the host formula of csrc/conv.hip (wrw_launch) and the kernel's
+    own slice start."""
     tiles = _cdiv(K, 64) * _cdiv(Co, 64) * B
     pix_chunks = min(max(1536 // max(tiles, 1), 1), max(M // 256, 1))
     pchunk = (_cdiv(M, pix_chunks) + 31) & ~31
@@ -213,7 +217,9 @@ def phase_list(HO, WO, kh, kw, Cin, pt, pl):
 
 
 def _fwd_launch(B, M, N, K, WO, stride, vm, vsv, sel=None):
-    """conv_fwd's choice of instantiation for one gather launch."""
+    """The instantiation and run-time stride of one gather launch: a mirror
+    of conv_fwd_variant in csrc/conv.hip, whose arguments are kept in
+    "ask"."""
     st = 0 if WO < 8 else stride
     tm = 32 if (_cdiv(M, 64) * _cdiv(N, 64) * B < 256 and M > 64) else 64
     if not vm:
@@ -225,19 +231,21 @@ def _fwd_launch(B, M, N, K, WO, stride, vm, vsv, sel=None):
     else:
         inst = (tm, 1, st if st in (1, 2) else 0, 1)
     return dict(kern="fwd<%d,%d,%d,%d>" % inst, KP=_kp64(K), WO=WO, M=M,
-                sel=sel, tm=tm, vst=inst[2])
+                sel=sel, tm=tm, vst=inst[2], stride=st,
+                ask=(B, M, N, WO, stride, vsv, not vm))
 
 
 def _wrw_launch(B, M, K, N, WO, st, vm, cols=None):
+    """Mirror of conv_wrw_variant (arguments in "ask") and the chunking."""
     if not vm:
-        kern = "wrw<0,0,1>"
+        kern = "wrw<0,0>"
     elif WO < 8 or st not in (1, 2):
-        kern = "wrw<1,0,1>"
+        kern = "wrw<1,0>"
     else:
-        kern = "wrw<1,%d,1>" % st
+        kern = "wrw<1,%d>" % st
     pix_chunks, pchunk, p0s = wrw_chunks(B, M, K, N)
     return dict(kern=kern, B=B, M=M, K=K, pix_chunks=pix_chunks,
-                PCHUNK=pchunk, p0s=p0s, cols=cols)
+                PCHUNK=pchunk, p0s=p0s, cols=cols, ask=(WO, st, not vm))
 
 
 def _direct3_staging(Hp, Wp, HO, WO, vp, Ci):
@@ -277,7 +285,9 @@ def _direct5_staging(Hp, Wp, HO, WO, vp):
 @functools.lru_cache(maxsize=None)
 def plan(c):
     """Every launch of one case's forward, backward-data and weight
-    gradient, as ops/conv.py and csrc/conv.hip select them."""
+    gradient, as ops/conv.py and csrc/conv.hip select them. route_f and
+    route_b name the kind of the forward and backward-data launches:
+    direct3, direct5, phase, gather, or flat (conv3d)."""
     B, Ci, Co = c.B, c.Ci, c.Co
     if c.kind == "conv3d":
         Dp, Hp, Wp = c.size
@@ -286,7 +296,8 @@ def plan(c):
         return dict(
             fwd=[_fwd_launch(B, Do * Ho * Wo, Co, K, Wo, 1, 0, 1)],
             dx=[_fwd_launch(B, Dp * Hp * Wp, Ci, Co * 18, Wp, 1, 0, 1)],
-            dw=[_wrw_launch(B, Do * Ho * Wo, K, Co, Wo, 1, 0)])
+            dw=[_wrw_launch(B, Do * Ho * Wo, K, Co, Wo, 1, 0)],
+            route_f="flat", route_b="flat")
     H, W = c.size
     kh, kw = c.k
     HO, WO = out_size(c)
@@ -305,6 +316,7 @@ def plan(c):
         elif st == 2 and dil == 1 and (kh, kw) == (5, 5) and Ci % 64 == 0:
             direct = 2
     phases_f = None
+    route_f = {2: "direct5", 1: "direct3"}.get(direct, "gather")
     if direct == 2:
         fwd = [dict(kern="direct5", KP=Ci * 25, vp=pt, sel=None,
                     staging=_direct5_staging(H, W, HO, WO, pt))]
@@ -312,6 +324,7 @@ def plan(c):
         fwd = [dict(kern="direct3", KP=Ci * 9, vp=pt, sel=None,
                     staging=_direct3_staging(H, W, HO, WO, pt, Ci))]
     elif sv == 2 and dil == 1:
+        route_f = "phase"
         phases_f = phase_list(HO, WO, kh, kw, Ci, pt, pl)
         fwd = [dict(_fwd_launch(B, p["nh"] * p["nw"], Co, p["Kp"], p["nw"],
                                 1, 1, 1, sel=(p["a"], p["b"])), phase=True)
@@ -320,11 +333,14 @@ def plan(c):
         fwd = [_fwd_launch(B, HO * WO, Co, K, WO, st, 1, sv)]
     ptb, plb = (kh - 1) * dil - pt, (kw - 1) * dil - pl
     phases_b = None
+    route_b = "gather"
     if sv == 1 and st == 1 and dil == 1 and (kh, kw) == (3, 3) \
             and Co % 64 == 0 and ptb == plb and ptb >= 1:
+        route_b = "direct3"
         dx = [dict(kern="direct3", KP=Co * 9, vp=ptb, sel=None,
                    staging=_direct3_staging(HO, WO, H, W, ptb, Co))]
     elif st == 2 and dil == 1:
+        route_b = "phase"
         phases_b = phase_list(H, W, kh, kw, Co, ptb, plb)
         dx = [dict(_fwd_launch(B, p["nh"] * p["nw"], Ci, p["Kp"], p["nw"],
                                1, 1, 1, sel=(p["a"], p["b"])), phase=True)
@@ -336,7 +352,7 @@ def plan(c):
                           cols=p["ktab"]) for p in phases_f]
     else:
         dw = [_wrw_launch(B, HO * WO, K, Co, WO, st, 1)]
-    return dict(fwd=fwd, dx=dx, dw=dw,
+    return dict(fwd=fwd, dx=dx, dw=dw, route_f=route_f, route_b=route_b,
                 nphase_f=None if phases_f is None else len(phases_f),
                 nphase_b=None if phases_b is None else len(phases_b))
 
@@ -401,7 +417,7 @@ FWD_INSTANTIATIONS = {"fwd<%d,%d,%d,%d>" % ((tm,) + v)
                       for tm in (32, 64)
                       for v in ((0, 0, 1), (1, 1, 1), (1, 2, 1), (1, 0, 1),
                                 (1, 1, 2), (1, 0, 2), (1, 0, 0))}
-WRW_INSTANTIATIONS = {"wrw<0,0,1>", "wrw<1,0,1>", "wrw<1,1,1>", "wrw<1,2,1>"}
+WRW_INSTANTIATIONS = {"wrw<0,0>", "wrw<1,0>", "wrw<1,1>", "wrw<1,2>"}
 # every kernel ops/conv.py can launch on the bf16 path, and every branch
 # docs/KERNELS.md lists as covered
 REQUIRED = (

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import _oracles_conv as O
+from dsin_amd import ops
 from dsin_amd.ops import conv as dconv
 
 IDS = [O.case_id(c) for c in O.ALL_CASES]
@@ -112,6 +113,129 @@ def test_phase_list_matches_ops():
             assert (m["a"], m["b"], m["nh"], m["nw"], m["Kp"]) == \
                 (t["a"], t["b"], t["nh"], t["nw"], t["Kp"])
             assert torch.equal(m["ktab"], t["ktab64"])
+
+
+# ------------------------------------- the mirror against what it mirrors
+
+def _ext():
+    ext = ops._try_load_ext()
+    assert ext is not None, "the extension must be built for these tests"
+    return ext
+
+
+def _geometry(c):
+    """(Cin, _Geom, direct_ok) of a 2D case's forward gather, from the case
+    alone, as conv2d / conv_transpose2d build it."""
+    kh, kw = c.k
+    if c.kind == "convT":
+        return c.Ci, dconv._Geom(1, c.stride, 1, kh, kw, kh - 1 - c.pad,
+                                 kw - 1 - c.pad), False
+    return c.Ci, dconv._Geom(c.stride, 1, c.dil, kh, kw, c.pad, c.pad), True
+
+
+@pytest.mark.parametrize("c", O.ALL_CASES, ids=IDS)
+def test_mirror_routes_as_ops_route(c):
+    """The kind of the forward and of the backward-data launches in plan()
+    (direct3 / direct5 / phase / gather, flat for conv3d) is what _route
+    answers for the case's geometry and for its transposed geometry."""
+    p = O.plan(c)
+    if c.kind == "conv3d":      # no routing: always the flat tables
+        assert (p["route_f"], p["route_b"]) == ("flat", "flat")
+        return
+    cin, g, direct_ok = _geometry(c)
+    assert p["route_f"] == dconv._route(cin, g, False, direct_ok)
+    assert p["route_b"] == dconv._route(c.Co, g.transposed(), True, True)
+    for route, launches in ((p["route_f"], p["fwd"]), (p["route_b"], p["dx"])):
+        for ln in launches:
+            assert ln["kern"] == route if route.startswith("direct") \
+                else ln["kern"].startswith("fwd<")
+            assert bool(ln.get("phase")) == (route == "phase")
+
+
+def test_route_asymmetries(monkeypatch):
+    """The choices of _route that no case of the table pins down alone,
+    asked directly; each decides which kernel a model layer runs."""
+    G, route = dconv._Geom, dconv._route
+    g3, g5 = G(1, 1, 1, 3, 3, 1, 1), G(2, 1, 1, 5, 5, 2, 2)
+    assert route(64, g3, False, True) == "direct3"
+    assert route(64, g3, True, True) == "direct3"       # backward-data too
+    assert route(64, g3, False, False) == "gather"      # conv-transpose fwd
+    assert route(65, g3, False, True) == "gather"       # Cin % 64
+    assert route(64, g3._replace(pt=0, pl=0), False, True) == "gather"
+    assert route(64, g3._replace(pt=2, pl=2), False, True) == "direct3"
+    assert route(64, g3._replace(pt=1, pl=2), True, True) == "gather"
+    assert route(64, g3._replace(dil=2), False, True) == "gather"
+    assert route(64, g5, False, True) == "direct5"
+    assert route(64, g5._replace(pt=0, pl=0), False, True) == "direct5"
+    assert route(64, g5, True, True) == "gather"        # never rotated
+    assert route(64, g5, False, False) == "gather"
+    assert route(32, g5, False, True) == "gather"
+    monkeypatch.setattr(dconv, "_DIRECT5", False)
+    assert route(64, g5, False, True) == "gather"
+    # phases: stuffed by 2 without dilation, whatever else holds
+    assert route(64, G(1, 2, 1, 3, 3, 1, 1), False, False) == "phase"
+    assert route(64, G(1, 2, 1, 3, 3, 1, 1), True, True) == "phase"
+    assert route(8, G(1, 2, 2, 3, 3, 2, 2), True, True) == "gather"
+    assert route(8, G(1, 3, 1, 3, 3, 1, 1), True, True) == "gather"
+    # the transposed geometry of backward-data
+    assert G(2, 1, 2, 3, 5, 1, 3).transposed() == G(1, 2, 2, 3, 5, 3, 5)
+
+
+@pytest.mark.parametrize("c", O.ALL_CASES, ids=IDS)
+def test_mirror_picks_the_extensions_instantiations(c):
+    """Every gather, phase and flat launch of plan() names the instantiation
+    and the run-time stride that conv_fwd_variant, the launch code's own
+    selection, returns for the same (B, M, N, WO, st, sv, flat); every
+    weight-gradient launch likewise against conv_wrw_variant."""
+    ext, p = _ext(), O.plan(c)
+    asked = 0
+    for ln in p["fwd"] + p["dx"]:
+        if ln["kern"].startswith("direct"):
+            continue
+        *inst, stride = ext.conv_fwd_variant(*ln["ask"])
+        assert ln["kern"] == "fwd<%d,%d,%d,%d>" % tuple(inst), ln["ask"]
+        assert ln["stride"] == stride, ln["ask"]
+        asked += 1
+    for ln in p["dw"]:
+        assert ln["kern"] == "wrw<%d,%d>" % ext.conv_wrw_variant(*ln["ask"])
+        asked += 1
+    assert asked >= 1
+
+
+def test_tile_rule_boundaries():
+    """The edges of the selection, asked of the extension directly."""
+    fv = _ext().conv_fwd_variant
+    # (B, M, N, WO, st, sv, flat) -> (TM, VM, VST, VSV, run-time stride)
+    assert fv(1, 64, 16, 8, 1, 1, False) == (64, 1, 1, 1, 1)   # M == 64
+    assert fv(1, 65, 16, 13, 1, 1, False)[0] == 32             # small grid
+    assert fv(1, 256 * 64, 64, 128, 1, 1, False)[0] == 64      # 256 groups
+    assert fv(1, 255 * 64, 64, 128, 1, 1, False)[0] == 32      # 255 groups
+    assert fv(4, 64 * 64, 64, 64, 1, 1, False)[0] == 64        # B counts
+    assert fv(1, 64 * 64, 4 * 64, 64, 1, 1, False)[0] == 64    # N tiles count
+    assert fv(1, 70, 16, 7, 1, 1, False) == (32, 1, 0, 1, 0)   # WO == 7
+    assert fv(1, 80, 16, 8, 1, 1, False) == (32, 1, 1, 1, 1)   # WO == 8
+    assert fv(1, 70, 16, 7, 2, 1, True) == (32, 0, 0, 1, 0)    # flat, WO < 8
+    assert fv(1, 80, 16, 8, 2, 1, True) == (32, 0, 0, 1, 2)
+    for tm, m in ((64, 64), (32, 4096)):
+        assert fv(1, m, 16, 64, 1, 3, False) == (tm, 1, 0, 0, 1)   # sv == 3
+        assert fv(1, m, 16, 64, 1, 2, False) == (tm, 1, 1, 2, 1)
+        assert fv(1, m, 16, 64, 2, 2, False) == (tm, 1, 0, 2, 2)
+        assert fv(1, m, 16, 64, 3, 1, False) == (tm, 1, 0, 1, 3)
+    wv = _ext().conv_wrw_variant
+    assert wv(8, 1, False) == (1, 1) and wv(7, 1, False) == (1, 0)
+    assert wv(8, 2, False) == (1, 2) and wv(8, 3, False) == (1, 0)
+    assert wv(8, 1, True) == (0, 0)
+
+
+def test_extension_has_the_named_conv_entry_points():
+    """The conv family is reached through entry points whose arguments all
+    mean something; the positional catch-alls are gone."""
+    ext = _ext()
+    for name in ("conv_direct", "conv_gather", "conv_flat", "conv_wrw_gather",
+                 "conv_wrw_flat", "conv_fwd_variant", "conv_wrw_variant"):
+        assert hasattr(ext, name), name
+    for name in ("conv_fwd", "conv_wrw"):
+        assert not hasattr(ext, name), name
 
 
 # ------------------------------------------------- geometry check (CPU only)

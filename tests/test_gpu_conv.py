@@ -249,8 +249,9 @@ def test_conv_fp8_path(dev):
 @pytest.mark.gpu
 def test_conv3x3_direct_path(dev):
     """Direct LDS-halo 3x3 kernel (stride 1, Ci%64==0) vs torch fp32:
-    forward + input/weight grads, odd sizes (edge-tile masking), and the
-    conv-transpose route (stuffed stride-1 3x3 with Co%64==0 backward)."""
+    forward + input/weight grads, odd sizes (edge-tile masking), and a
+    stride-2 3x3 conv-transpose with 64-multiple channels, which stays off
+    the direct path both ways."""
     from dsin_amd.ops import conv as dconv
     torch.manual_seed(1)
     for Ci, Co, H, W in [(64, 48, 24, 40), (128, 128, 19, 29)]:
@@ -271,8 +272,9 @@ def test_conv3x3_direct_path(dev):
         dwmax = w2.grad.abs().max().item()
         assert torch.allclose(w1.grad.float(), w2.grad,
                               atol=0.02 * max(dwmax, 1.0), rtol=0.05)
-    # conv-transpose: backward-data of the stuffed conv takes the direct
-    # path when Co%64==0
+    # conv-transpose, stride 2 (sv == 2): the forward runs as four phases
+    # and its backward-data is the stride-2 gather, not the direct kernel,
+    # Co%64==0 or not (only a stride-1 conv-transpose has a direct dx)
     xt = torch.randn(1, 128, 10, 14, device=dev).requires_grad_(True)
     wt = torch.randn(128, 64, 3, 3, device=dev) * 0.05
     wt1 = wt.clone().requires_grad_(True)
