@@ -176,8 +176,8 @@ def _wmat(w1: torch.Tensor, fp8: bool = False, direct: bool = False,
           khw: int = 9) -> torch.Tensor:
     """(Co, K) any-dtype -> bf16 (or e4m3-as-uint8) zero-padded to
     (Co, KP64+8); the zeros cancel the clamped out-of-range A gathers.
-    direct: (chunk, tap, ci) mode-2 layout for the direct LDS-halo kernels
-    (khw = 9 for 3x3, 25 for 5x5/s2)."""
+    direct: (chunk, tap, ci) layout for the direct LDS-halo kernels: khw =
+    25 (5x5/s2) mode 2, khw = 9 (3x3) its fragment-major form, mode 6."""
     K = w1.shape[1]
     if fp8:
         def build8():
@@ -193,7 +193,8 @@ def _wmat(w1: torch.Tensor, fp8: bool = False, direct: bool = False,
             w1, ("d", khw) if direct else "p",
             lambda: _require_ext("wmat_make")(w1.contiguous(),
                                               khw if direct else 1,
-                                              2 if direct else 0))
+                                              (6 if khw == 9 else 2)
+                                              if direct else 0))
     KP = (K + 63) & ~63
     return F.pad(w1.to(torch.bfloat16), (0, KP + 8 - K)).contiguous()
 
@@ -202,11 +203,12 @@ def _wmat_rot(w1: torch.Tensor, khw: int, direct: bool = False) -> torch.Tensor:
     """Padded bf16 W panel for the backward-data gather conv: spatial taps
     reversed and cin<->cout swapped — one kernel instead of the torch
     flip+permute+reshape+pad chain (~4 kernels per conv backward). direct:
-    mode-3 (chunk, tap, ci) layout for the 3x3 direct kernel."""
+    the fragment-major (chunk, tap, ci) layout of the 3x3 direct kernel,
+    mode 7."""
     return _wmat_cache(
         w1, ("rd" if direct else "r", khw),
         lambda: _require_ext("wmat_make")(w1.contiguous(), khw,
-                                          3 if direct else 1))
+                                          7 if direct else 1))
 
 
 def _act_grad(dy: torch.Tensor, y_act, act: int) -> torch.Tensor:

@@ -100,8 +100,9 @@ static const float* bias_ptr(const c10::optional<torch::Tensor>& bias) {
   return bias->data_ptr<float>();
 }
 
-// Direct LDS-halo kernels (virtual pad vpad; wmat in the mode-2/3 layout of
-// wmat_make): ksize 3 is the stride-1 3x3, ksize 5 the stride-2 5x5.
+// Direct LDS-halo kernels (virtual pad vpad): ksize 3 is the stride-1 3x3,
+// wmat the fragment-major panel of wmat_make mode 6/7; ksize 5 the stride-2
+// 5x5, wmat in the mode-2 layout.
 torch::Tensor conv_direct(torch::Tensor x, torch::Tensor wmat,
                           c10::optional<torch::Tensor> bias, int64_t N,
                           int64_t HO, int64_t WO, int64_t act, int64_t vpad,
@@ -113,6 +114,8 @@ torch::Tensor conv_direct(torch::Tensor x, torch::Tensor wmat,
   TORCH_CHECK((ksize == 3 || ksize == 5) && Ci % 64 == 0,
               "direct conv gate mismatch: ksize 3 or 5, Ci % 64 == 0");
   TORCH_CHECK(wmat.size(1) == KPd + CONV_AP, "direct wmat stride mismatch");
+  TORCH_CHECK(wmat.size(0) == (ksize == 3 ? (N + 15) & ~15 : N),
+              "direct wmat rows mismatch (3x3: 16-row fragment groups)");
   TORCH_CHECK(HO == (Hp + 2 * vpad - ksize) / stride + 1 &&
                   WO == (Wp + 2 * vpad - ksize) / stride + 1,
               "direct conv size mismatch");
@@ -327,9 +330,14 @@ torch::Tensor wmat_make(torch::Tensor w1, int64_t khw, int64_t mode) {
   CHECK_CUDA_CONTIG(w1);
   const int64_t N = w1.size(0), K = w1.size(1);
   const bool rot = (mode & 1) != 0;
-  const int64_t rows = rot ? K / khw : N;
+  const int64_t nrows = rot ? K / khw : N;
   const int64_t kout = rot ? N * khw : K;
   const int64_t KPA = ((kout + 63) & ~63) + CONV_AP;
+  TORCH_CHECK(mode >= 0 && mode <= 7 && mode != 4 && mode != 5,
+              "wmat_make: mode 0-3, 6 or 7");
+  TORCH_CHECK(!(mode & 4) || kout % 64 == 0,
+              "wmat_make: fragment-major panels need K % 64 == 0");
+  const int64_t rows = (mode & 4) ? (nrows + 15) & ~15 : nrows;
   auto out = torch::empty({rows, KPA},
                           w1.options().dtype(torch::kBFloat16));
   const long long total = rows * KPA;
@@ -339,13 +347,13 @@ torch::Tensor wmat_make(torch::Tensor w1, int64_t khw, int64_t mode) {
     hipLaunchKernelGGL((wmat_make_kernel<float>), dim3(grid), dim3(256), 0,
                        stream, w1.data_ptr<float>(), (cvbf16*)out.data_ptr(),
                        (int)rows, (int)kout, (int)K, (int)khw, (int)KPA,
-                       (int)mode);
+                       (int)mode, (int)nrows);
   } else {
     TORCH_CHECK(w1.scalar_type() == torch::kBFloat16, "wmat_make: fp32/bf16");
     hipLaunchKernelGGL((wmat_make_kernel<cvbf16>), dim3(grid), dim3(256), 0,
                        stream, (const cvbf16*)w1.data_ptr(),
                        (cvbf16*)out.data_ptr(), (int)rows, (int)kout, (int)K,
-                       (int)khw, (int)KPA, (int)mode);
+                       (int)khw, (int)KPA, (int)mode, (int)nrows);
   }
   return out;
 }

@@ -504,8 +504,9 @@ void conv_fwd_kernel(const cvbf16* __restrict__ xpad,   // see VM note above
 // this kernel stages each 8x8-output tile's 10x10 input halo ONCE per
 // 64-channel chunk in LDS (pixel-major, channels contiguous) and runs all
 // nine taps out of LDS: 9x less gather traffic and 72 MFMAs between
-// barriers (one barrier per ci-chunk). W panel layout is (chunk, tap, ci)
-// -- wmat_make mode 2/3.
+// barriers (one barrier per ci-chunk). W panel: k in (chunk, tap, ci)
+// order, stored fragment-major -- wmat_make mode 6/7 -- because the vector
+// memory path, not LDS or the MFMAs, bounds this kernel (docs/KERNELS.md).
 //   out[n][oy0+py][ox0+px] = sum_{ci,r,s} xpad[ci][oy0+py+r][ox0+px+s]
 //                                        * w[n][(ci,r,s)]
 // vp: VIRTUAL symmetric pad — when nonzero, xpad is an UNPADDED tensor
@@ -543,7 +544,13 @@ void conv3x3_direct_kernel(const cvbf16* __restrict__ xpad, // (Ci, Hp, Wp)
   const int n0 = blockIdx.y * CONV_TN + wid * 16;
   const int ncol = n0 + colL;
   const int WSTRIDE = KP + CONV_AP;
-  const cvbf16* wrow = wmat + (long long)(ncol < N ? ncol : 0) * WSTRIDE;
+  // fragment-major panel (wmat_make mode 6/7): the wave's 16 couts are one
+  // row group, whose B fragments of 32-deep k-step h are the 1 KiB at
+  // group*16*WSTRIDE + h*512, in lane order: one coalesced load per k-step
+  // instead of 64 scattered 16-byte pieces of 16 panel rows. A group wholly
+  // past N reads group 0 (its outputs are never stored).
+  const cvbf16* wfrag =
+      wmat + (long long)((n0 < N ? n0 : 0) >> 4) * 16 * WSTRIDE + lane * 8;
 
   cv_f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f},
                      {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
@@ -631,7 +638,7 @@ void conv3x3_direct_kernel(const cvbf16* __restrict__ xpad, // (Ci, Hp, Wp)
 #pragma unroll
     for (int j = 0; j < 2; ++j)
       wset[j] = *reinterpret_cast<const cv_bf16x8*>(
-          &wrow[kbase + j * 32 + kgrp * 8]);
+          &wfrag[(kbase + j * 32) * 16]);
   };
 
   stage(0, 0);
@@ -1061,18 +1068,31 @@ __global__ void act_bwd_kernel(const T* __restrict__ dy,
 //   2: direct-conv layout k' = (ci/64)*64*khw + t*64 + ci%64 (channels
 //      contiguous per tap per 64-chunk — see conv3x3_direct_kernel)
 //   3: mode 1 + mode 2 (rotated weights in direct layout)
+//   6, 7: mode 2, 3 stored fragment-major for conv3x3_direct_kernel: rows
+//      in groups of 16 (zero rows fill the last group), each group
+//      16*KPA elements holding [k'/32][lane][8] with lane = 16*kgrp + row,
+//      k' = 32*step + 8*kgrp + e — the 64 lanes' MFMA B fragments of one
+//      32-deep k-step are one contiguous 1 KiB
 // k >= K -> 0.
 template <typename T>
 __global__ void wmat_make_kernel(const T* __restrict__ w1,
                                  cvbf16* __restrict__ out,
                                  int rows, int kout, int kin, int khw,
-                                 int KPA, int mode) {
+                                 int KPA, int mode, int nrows) {
+  // rows: rows of out (modes 6, 7: padded to 16); nrows: rows that w1 fills
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long total = (long long)rows * KPA;
   long long gstride = (long long)gridDim.x * blockDim.x;
   for (; i < total; i += gstride) {
-    const int n = (int)(i / KPA);
+    int n = (int)(i / KPA);
     int k = (int)(i % KPA);
+    if (mode & 4) {
+      const int rem = (int)(i % (16LL * KPA));
+      const int ln = (rem & 511) >> 3;
+      n = (int)(i / (16LL * KPA)) * 16 + (ln & 15);
+      k = (rem >> 9) * 32 + (ln >> 4) * 8 + (rem & 7);
+      if (rem >= 16 * kout || n >= nrows) k = kout;  // group tail, pad rows
+    }
     float v = 0.f;
     if (k < kout) {
       if (mode >= 2) {   // decode direct layout: k' -> (c, tap, ci_in_chunk)
