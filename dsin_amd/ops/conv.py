@@ -10,7 +10,7 @@ torch-differentiable geometry transforms:
     xv = pad(stuff(x, sv)) exists only VIRTUALLY: the staging bounds-tests
     packed coordinate tables against the raw tensor and produces zeros for
     the pad ring and stuff holes (no padded buffer, no pad kernel, no
-    extra HBM round trip — round-1's pad_stuff path cost ~2 ms/step);
+    extra HBM round trip);
   * backward-data is the SAME gather (_gather) on the raw dy with the
     transposed virtual geometry ((st', sv', pads') = (sv, st, (k-1)*dil -
     pads)) and spatially-rotated ci<->co-swapped weights; _route picks the
@@ -23,8 +23,10 @@ torch-differentiable geometry transforms:
 
 bf16 compute with fp32 accumulate; fp32 master weights. Optional fused
 epilogue activation (relu / leaky-0.2) for the no-batchnorm convs (siNet).
-The fp8 (e4m3) path keeps explicit pad buffers: its pad kernel doubles as
-the float->e4m3 quantizer, which is needed regardless.
+The fp8 (e4m3) path keeps explicit pad buffers (pad_stuff_e4m3): its pad
+kernel doubles as the float->e4m3 quantizer, which is needed regardless.
+conv3d (VALID, stride 1) runs the same gather kernels over flat-offset
+tables on its own pre-padded input.
 CPU path falls back to torch.nn.functional (the numerics oracle).
 """
 
@@ -368,10 +370,10 @@ class _GatherConvFP8Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, bias, stride, dil, kh, kw, HO, WO, act, pads,
                 stuff):
-        pad_fn = _require_ext("pad_stuff")
+        pad_fn = _require_ext("pad_stuff_e4m3")
         ext_fwd = _require_ext("conv_flat")
         pl, pr, pt, pb = pads
-        xbuf = pad_fn(x.contiguous(), pt, pb, pl, pr, stuff, True)
+        xbuf = pad_fn(x.contiguous(), pt, pb, pl, pr, stuff)
         B, Ci, Hp, Wp = xbuf.shape
         Co, K = w1.shape
         mbase, koff = _plan(x.device, Ci, Hp, Wp, kh, kw, stride, dil, HO, WO)
@@ -388,7 +390,7 @@ class _GatherConvFP8Fn(torch.autograd.Function):
         xbuf, w1, y_act = ctx.saved_tensors
         (stride, dil, kh, kw, HO, WO, has_bias, act, pads, stuff, xshape,
          xdtype) = ctx.meta
-        pad_fn = _require_ext("pad_stuff")
+        pad_fn = _require_ext("pad_stuff_e4m3")
         ext_fwd = _require_ext("conv_flat")
         ext_wrw = _require_ext("conv_wrw_flat")
         B, Ci, Hp, Wp = xbuf.shape
@@ -401,13 +403,13 @@ class _GatherConvFP8Fn(torch.autograd.Function):
                                                         device=dy.device))
         elif act == 2:
             dy = torch.where(y_act > 0, dy, dy * 0.2)
-        dy8 = pad_fn(dy, 0, 0, 0, 0, 1, True).view(B, Co, HO, WO)
+        dy8 = pad_fn(dy, 0, 0, 0, 0, 1).view(B, Co, HO, WO)
 
         dx = None
         if ctx.needs_input_grad[0]:
             with torch.no_grad():
                 pe_h, pe_w = (kh - 1) * dil, (kw - 1) * dil
-                dybuf = pad_fn(dy, pe_h, pe_h, pe_w, pe_w, stride, True)
+                dybuf = pad_fn(dy, pe_h, pe_h, pe_w, pe_w, stride)
                 wrot = (w1.view(Co, Ci, kh, kw).flip(2, 3).permute(1, 0, 2, 3)
                         .reshape(Ci, Co * kh * kw))
                 mb2, ko2 = _plan(dy.device, Co, dybuf.shape[2], dybuf.shape[3],

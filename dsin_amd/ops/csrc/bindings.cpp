@@ -62,8 +62,8 @@ void adam_step(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                torch::Tensor v, torch::Tensor lr, torch::Tensor step,
                c10::optional<torch::Tensor> wd, double b1, double b2,
                double eps);
-torch::Tensor pad_stuff(torch::Tensor x, int64_t pt, int64_t pb, int64_t pl,
-                        int64_t pr, int64_t stride, bool fp8);
+torch::Tensor pad_stuff_e4m3(torch::Tensor x, int64_t pt, int64_t pb,
+                             int64_t pl, int64_t pr, int64_t stride);
 std::vector<torch::Tensor> bn_fwd(torch::Tensor y, torch::Tensor gamma,
                                   torch::Tensor beta, torch::Tensor rmean,
                                   torch::Tensor rvar, double momentum,
@@ -168,7 +168,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("panel_gather", &dsin::panel_gather,
         "column-gather of a W panel (phase-decomposed convs)");
   m.def("adam_step", &dsin::adam_step, "fused flat-buffer Adam step");
-  m.def("pad_stuff", &dsin::pad_stuff, "fused pad/zero-stuff/cast to bf16");
+  m.def("pad_stuff_e4m3", &dsin::pad_stuff_e4m3,
+        "fused pad/zero-stuff/quantize to e4m3 (the fp8 conv input buffer)",
+        py::arg("x"), py::arg("pt"), py::arg("pb"), py::arg("pl"),
+        py::arg("pr"), py::arg("stride"));
   m.def("bn_fwd", &dsin::bn_fwd, "fused batch-norm(+act) forward");
   m.def("bn_bwd", &dsin::bn_bwd, "fused batch-norm(+act) backward");
   m.def("heatmap_mask_fwd", &dsin::heatmap_mask_fwd,

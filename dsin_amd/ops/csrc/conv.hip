@@ -113,6 +113,8 @@ torch::Tensor conv_direct(torch::Tensor x, torch::Tensor wmat,
   const int64_t KPd = (Ci * ksize * ksize + 63) & ~63;
   TORCH_CHECK((ksize == 3 || ksize == 5) && Ci % 64 == 0,
               "direct conv gate mismatch: ksize 3 or 5, Ci % 64 == 0");
+  TORCH_CHECK(ksize != 3 || vpad >= 1,
+              "direct 3x3 conv needs a virtual pad of at least 1");
   TORCH_CHECK(wmat.size(1) == KPd + CONV_AP, "direct wmat stride mismatch");
   TORCH_CHECK(wmat.size(0) == (ksize == 3 ? (N + 15) & ~15 : N),
               "direct wmat rows mismatch (3x3: 16-row fragment groups)");
@@ -208,12 +210,15 @@ torch::Tensor conv_gather(torch::Tensor x, torch::Tensor wmat,
                        pt, pl, false, out, oh0, ow0, ostep);
 }
 
-// Flat-offset tables over a pre-padded buffer: bf16 (conv3d) or e4m3.
+// Flat-offset tables over a pre-padded buffer: bf16 (conv3d, stride 1) or
+// e4m3 (stride 1 or 2).
 torch::Tensor conv_flat(torch::Tensor xbuf, torch::Tensor wmat,
                         c10::optional<torch::Tensor> bias,
                         torch::Tensor mbase, torch::Tensor koff, int64_t N,
                         int64_t K, int64_t HO, int64_t WO, int64_t act,
                         int64_t stride) {
+  TORCH_CHECK(xbuf.scalar_type() == torch::kByte || stride == 1,
+              "conv_flat: the bf16 flat staging is stride 1 only");
   return gather_launch(xbuf, wmat, bias, mbase, koff, N, K, HO, WO, act,
                        stride, 1, 0, 0, true, c10::nullopt, 0, 0, 1);
 }
@@ -258,7 +263,7 @@ static torch::Tensor wrw_launch(torch::Tensor x, torch::Tensor dy,
                        (const cvbf16*)dy.data_ptr(), dwp.data_ptr<float>(),
                        mtab.data_ptr<int>(), ktab.data_ptr<int>(), (int)M,
                        (int)N, (int)K, x.stride(0), dy.stride(0), pix_chunks,
-                       (int)WO, (int)mcontig, (int)st, (int)x.size(2),
+                       (int)WO, (int)st, (int)x.size(2),
                        (int)x.size(3), (int)pt, (int)pl);
   }
   if (B * pix_chunks == 1) return dwp.view({N, K});
@@ -272,10 +277,13 @@ torch::Tensor conv_wrw_gather(torch::Tensor x, torch::Tensor dy,
   return wrw_launch(x, dy, mpack, kpack, N, K, WO, false, st, pt, pl, false);
 }
 
-// mcontig: 8 pixels of an output row are contiguous in xbuf (flat staging only)
+// mcontig: 8 pixels of an output row are contiguous in xbuf. The bf16
+// kernel takes that for granted (stride 1); e4m3 may pass false.
 torch::Tensor conv_wrw_flat(torch::Tensor xbuf, torch::Tensor dy,
                             torch::Tensor mbase, torch::Tensor koff, int64_t N,
                             int64_t K, int64_t WO, bool mcontig) {
+  TORCH_CHECK(xbuf.scalar_type() == torch::kByte || mcontig,
+              "conv_wrw_flat: the bf16 flat staging needs mcontig");
   return wrw_launch(xbuf, dy, mbase, koff, N, K, WO, mcontig, 1, 0, 0, true);
 }
 

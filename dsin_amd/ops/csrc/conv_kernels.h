@@ -70,7 +70,7 @@ __global__ void conv_tables_kernel(int* __restrict__ mbase,
 // of flat offsets into a pre-padded buffer, each entry carries 2D (or
 // channel+2D) coordinates so the staging can bounds-test against the REAL
 // tensor and produce zeros for the pad/stuff positions — no padded buffer,
-// no pad_stuff kernel, no extra HBM round trip per conv.
+// no pad kernel, no extra HBM round trip per conv.
 //   mpack[m] = (oh*stride) << 16 | (ow*stride)        (virtual-image coords)
 //   kpack[k] = ci << 20 | (r*dil) << 10 | (s*dil)
 // Field limits: ow*stride < 65536, oh*stride < 32768 and ci < 2048 (the
@@ -98,18 +98,37 @@ __global__ void conv_tables_v2_kernel(int* __restrict__ mpack,
 typedef __attribute__((ext_vector_type(8))) unsigned short cv_u16x8;
 typedef __attribute__((ext_vector_type(4))) unsigned short cv_u16x4;
 
+// x[a] if ok, else 0, as bf16 bits: THE element load of every staging path
+// that may touch a pad, a stuff hole or a border. The caller clamps a into
+// the tensor, so the load is unconditional and the select comes after it.
+// Keep it so: an if-guarded load makes hipcc branch around each load and
+// wait vmcnt(0) per element (measured: 175 vmcnt(0) in the staging, ~7x
+// kernel slowdown).
+__device__ __forceinline__ unsigned short cv_load_or_zero(const cvbf16* x,
+                                                          long long a,
+                                                          bool ok) {
+  const cvbf16 v = x[a];
+  return ok ? *reinterpret_cast<const unsigned short*>(&v) : (unsigned short)0;
+}
+
+// Epilogue value of the three forward kernels: bias, then act (0 none,
+// 1 ReLU, 2 leaky 0.2).
+__device__ __forceinline__ float cv_bias_act(float v, float bv, int act) {
+  v += bv;
+  if (act == 1) v = fmaxf(v, 0.f);
+  else if (act == 2) v = fmaxf(v, 0.2f * v);
+  return v;
+}
+
 // Stage one 8-element run from the virtual image pad(stuff(x, SV)) at
 // virtual coords (hv, wv0 + i*ST), i = 0..7 (pads already subtracted by the
 // caller). Elements outside the real tensor (pad region, stuff zeros,
 // borders) come out 0. Vector reads only where provably in-row; the guarded
 // per-element path touches only valid addresses, so no slack allocation or
 // address clamping is needed.
-// BRANCHLESS by construction: the border path issues 8 unconditional
-// clamped scalar loads and zero-selects afterwards — an if-guarded load
-// per element makes hipcc branch around each load and wait vmcnt(0) per
-// element (measured: 175 vmcnt(0) in the staging, ~7x kernel slowdown).
-// Every address stays inside the image: rows clamp into [0, H) and columns
-// into [0, W).
+// The border path never guards a load: it is 8 cv_load_or_zero (written
+// out in the SV == 1 half, see there). Every address stays inside the
+// image: rows clamp into [0, H) and columns into [0, W).
 template <int ST, int SV>
 __device__ __forceinline__ void vstage8(const cvbf16* __restrict__ x,
                                         int H, int W, int ci, int hv,
@@ -135,6 +154,9 @@ __device__ __forceinline__ void vstage8(const cvbf16* __restrict__ x,
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int c = wv0 + i * ST;
+        // cv_load_or_zero written out: through the helper hipcc schedules
+        // this loop differently and the TM=32 gather kernels go from 96 to
+        // 104 VGPRs, a wave per SIMD (profiles/r12_conv_device.md)
         const cvbf16 v = x[row + min(max(c, 0), wmax)];
         out[i] = (rok && (unsigned)c < (unsigned)W)
                      ? *reinterpret_cast<const unsigned short*>(&v)
@@ -161,10 +183,9 @@ __device__ __forceinline__ void vstage8(const cvbf16* __restrict__ x,
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int c = wv0 + i;
-        const cvbf16 v = x[row + min(max(c >> 1, 0), wmax)];
-        out[i] = (rok && !(c & 1) && (unsigned)(c >> 1) < (unsigned)W)
-                     ? *reinterpret_cast<const unsigned short*>(&v)
-                     : (unsigned short)0;
+        out[i] = cv_load_or_zero(
+            x, row + min(max(c >> 1, 0), wmax),
+            rok && !(c & 1) && (unsigned)(c >> 1) < (unsigned)W);
       }
     }
   }
@@ -175,14 +196,15 @@ __device__ __forceinline__ void vstage8(const cvbf16* __restrict__ x,
 // which at TM=64 launch only ~600 workgroups on 256 CUs and run
 // latency-bound at ~2.3 waves/SIMD). The host picks 32 when the TM=64 grid
 // would underfill the chip.
-// VM=0: flat-offset tables over a pre-padded buffer (legacy; conv3d).
+// VM=0: flat-offset tables over a pre-padded buffer (conv3d). Run-time
+// `stride` is 1 (vector staging) or 0 (per-element staging of rows narrower
+// than 8 pixels); the host refuses any other.
 // VM=1: packed-coordinate tables + VIRTUAL pad/stuff — xpad is the RAW
 // (Ci, vH, vW) tensor and staging zero-masks the pad ring and stuff holes
-// (vpt/vpl = virtual pads, vsv = stuff stride). Kills the pad_stuff kernel
-// and the padded-buffer HBM round trip per conv. VST/VSV are the
-// COMPILE-TIME conv stride / stuff stride for VM=1 (VST=0 = generic
-// per-element path for narrow outputs); runtime `stride`/`vsv` args are
-// used by the VM=0 path and must match VST/VSV when VM=1. VSV=0 (with
+// (vpt/vpl = virtual pads, vsv = stuff stride): no padded copy of the
+// tensor per conv. VST/VSV are the COMPILE-TIME conv stride / stuff stride
+// (VST=0 = generic per-element path for narrow outputs); the run-time
+// `stride`/`vsv` args must match VST/VSV. VSV=0 (with
 // VST=0 only) takes the stuff stride from the runtime `vsv`: the
 // backward-data gather of a conv whose stride is 3 or more.
 template <int TM, int VM, int VST, int VSV>
@@ -261,8 +283,14 @@ void conv_fwd_kernel(const cvbf16* __restrict__ xpad,   // see VM note above
   const cvbf16* wrow = wmat + (long long)(ncol < N ? ncol : 0) * WSTRIDE;
 
   typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
-  u16x8 stage[NST];
-  cv_bf16x8 wfrag[2];
+  // one register set of the software pipeline below: a staged A chunk, its
+  // two W fragments, and the k offsets of the chunk the set stages next
+  struct RegSet {
+    u16x8 stage[NST];
+    cv_bf16x8 wfrag[2];
+    int ko[NST];
+  };
+  RegSet sA, sB;
 
   auto load_half = [&](int ko, u16x8& st) {
     if (VM) {
@@ -308,9 +336,7 @@ void conv_fwd_kernel(const cvbf16* __restrict__ xpad,   // see VM note above
             a = ((long long)kci * vH + min(max(hv, 0), vH - 1)) * vW +
                 min(max(wv, 0), vW - 1);
           }
-          const cvbf16 v = x[a];
-          st[i] = ok ? *reinterpret_cast<const unsigned short*>(&v)
-                     : (unsigned short)0;
+          st[i] = cv_load_or_zero(x, a, ok);
         }
       }
       return;
@@ -321,19 +347,7 @@ void conv_fwd_kernel(const cvbf16* __restrict__ xpad,   // see VM note above
           &x[max(mb1 + ko, 0)]);
 #pragma unroll
       for (int i = 0; i < 8; ++i) st[i] = (i < cross) ? a[i] : b[i];
-    } else if (stride == 2) {
-      const int b0 = mb0 + ko;
-      const int b1 = max(mb1 + ko, 0);
-      const u16x8 a0 = *reinterpret_cast<const u16x8*>(&x[b0]);
-      const u16x8 a1 = *reinterpret_cast<const u16x8*>(&x[b0 + 8]);
-      const u16x8 c0 = *reinterpret_cast<const u16x8*>(&x[b1]);
-      const u16x8 c1 = *reinterpret_cast<const u16x8*>(&x[b1 + 8]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        st[i] = (i < cross) ? a0[2 * i] : c0[2 * i];
-        st[4 + i] = (4 + i < cross) ? a1[2 * i] : c1[2 * i];
-      }
-    } else {
+    } else {  // stride == 0: narrow rows, per element
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int gm = min(m0 + sm8 + i, M - 1);
@@ -347,21 +361,21 @@ void conv_fwd_kernel(const cvbf16* __restrict__ xpad,   // see VM note above
   // was the dominant stall (each set stages every other chunk, so its next
   // k offsets are +2*KC ahead).
   auto ko_at = [&](int k) { return (k < K) ? koff[k] : 0; };
-  int koA[NST], koB[NST];
 #pragma unroll
   for (int h = 0; h < NST; ++h) {
-    koA[h] = ko_at(h * KCOV + sk);
-    koB[h] = ko_at(KC + h * KCOV + sk);
+    sA.ko[h] = ko_at(h * KCOV + sk);
+    sB.ko[h] = ko_at(KC + h * KCOV + sk);
   }
-  auto load_chunk = [&](int kc) {
+  auto load_set = [&](RegSet& s, int kc) {
     // W first: its consumer (the MFMA phase) waits on it with a counted
     // vmcnt that leaves the later A loads in flight
-    wfrag[0] = *reinterpret_cast<const cv_bf16x8*>(&wrow[kc + kgrp * 8]);
-    wfrag[1] = *reinterpret_cast<const cv_bf16x8*>(&wrow[kc + 32 + kgrp * 8]);
+    s.wfrag[0] = *reinterpret_cast<const cv_bf16x8*>(&wrow[kc + kgrp * 8]);
+    s.wfrag[1] =
+        *reinterpret_cast<const cv_bf16x8*>(&wrow[kc + 32 + kgrp * 8]);
 #pragma unroll
-    for (int h = 0; h < NST; ++h) load_half(koA[h], stage[h]);
+    for (int h = 0; h < NST; ++h) load_half(s.ko[h], s.stage[h]);
 #pragma unroll
-    for (int h = 0; h < NST; ++h) koA[h] = ko_at(kc + 2 * KC + h * KCOV + sk);
+    for (int h = 0; h < NST; ++h) s.ko[h] = ko_at(kc + 2 * KC + h * KCOV + sk);
   };
   // A-tile byte-address XOR swizzle (see write/read pair): staging writes at
   // an 8-row stride collide on banks; rows stay 16B aligned and 128B blocks
@@ -384,45 +398,24 @@ void conv_fwd_kernel(const cvbf16* __restrict__ xpad,   // see VM note above
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
       rd_off[kk * MI + mi] = aswz(mi * 16 + colL, kk * 32 + kgrp * 8);
-  auto write_chunk = [&](int buf) {
+  auto write_set = [&](const RegSet& s, int buf) {
     char* dst = As8 + buf * ABUF * 2;
 #pragma unroll
     for (int h = 0; h < NST; ++h)
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        unsigned short u = stage[h][i];
+        unsigned short u = s.stage[h][i];
         *reinterpret_cast<cvbf16*>(&dst[wr_off[h * 8 + i]]) =
             *reinterpret_cast<cvbf16*>(&u);
       }
   };
 
-  // 2-deep software pipeline: 4 LDS buffers, two register stage sets.
-  // Invariant at iteration kt (even): buf[kt&3] holds chunk kt, set S1
-  // holds chunk kt+1; the body issues loads for chunk kt+2 into S0, MFMAs
-  // chunk kt, writes S1 into buf[(kt+1)&3], barriers; odd iterations swap
+  // 2-deep software pipeline: 4 LDS buffers, the two register sets.
+  // Invariant at iteration kt (even): buf[kt&3] holds chunk kt, set B
+  // holds chunk kt+1; the body issues loads for chunk kt+2 into A, MFMAs
+  // chunk kt, writes B into buf[(kt+1)&3], barriers; odd iterations swap
   // the sets. A-prefetch therefore has ~two MFMA phases to land.
   const int nchunks = KP / KC;
-  u16x8 stageB[NST];
-  cv_bf16x8 wfragB[2];
-  auto load_chunkB = [&](int kc) {
-    wfragB[0] = *reinterpret_cast<const cv_bf16x8*>(&wrow[kc + kgrp * 8]);
-    wfragB[1] = *reinterpret_cast<const cv_bf16x8*>(&wrow[kc + 32 + kgrp * 8]);
-#pragma unroll
-    for (int h = 0; h < NST; ++h) load_half(koB[h], stageB[h]);
-#pragma unroll
-    for (int h = 0; h < NST; ++h) koB[h] = ko_at(kc + 2 * KC + h * KCOV + sk);
-  };
-  auto write_chunkB = [&](int buf) {
-    char* dst = As8 + buf * ABUF * 2;
-#pragma unroll
-    for (int h = 0; h < NST; ++h)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        unsigned short u = stageB[h][i];
-        *reinterpret_cast<cvbf16*>(&dst[wr_off[h * 8 + i]]) =
-            *reinterpret_cast<cvbf16*>(&u);
-      }
-  };
   auto mfma_chunk = [&](int kt, const cv_bf16x8* w2) {
     const char* cur = As8 + (kt & 3) * ABUF * 2;
 #pragma unroll
@@ -437,34 +430,34 @@ void conv_fwd_kernel(const cvbf16* __restrict__ xpad,   // see VM note above
     }
   };
 
-  load_chunk(0);              // -> stage/wfrag (set A)
-  write_chunk(0);
-  cv_bf16x8 wA[2] = {wfrag[0], wfrag[1]};
+  load_set(sA, 0);
+  write_set(sA, 0);
+  cv_bf16x8 wA[2] = {sA.wfrag[0], sA.wfrag[1]};
   cv_bf16x8 wB[2] = {wA[0], wA[1]};
   if (nchunks > 1) {
-    load_chunkB(KC);          // chunk 1 -> set B
-    wB[0] = wfragB[0];
-    wB[1] = wfragB[1];
+    load_set(sB, KC);         // chunk 1
+    wB[0] = sB.wfrag[0];
+    wB[1] = sB.wfrag[1];
   }
   __syncthreads();
 
   for (int kt = 0; kt + 1 < nchunks; kt += 2) {
     // even iteration: compute chunk kt (in buf kt&3), set B holds kt+1
-    if (kt + 2 < nchunks) load_chunk((kt + 2) * KC);
+    if (kt + 2 < nchunks) load_set(sA, (kt + 2) * KC);
     mfma_chunk(kt, wA);
-    write_chunkB((kt + 1) & 3);
+    write_set(sB, (kt + 1) & 3);
     __syncthreads();
     // odd iteration: compute chunk kt+1, set A holds kt+2
-    if (kt + 3 < nchunks) load_chunkB((kt + 3) * KC);
+    if (kt + 3 < nchunks) load_set(sB, (kt + 3) * KC);
     mfma_chunk(kt + 1, wB);
-    wA[0] = wfrag[0];   // W(kt+2): copied only after both MFMA phases so
-    wA[1] = wfrag[1];   // its wait never stalls the matrix pipe
+    wA[0] = sA.wfrag[0];   // W(kt+2): copied only after both MFMA phases so
+    wA[1] = sA.wfrag[1];   // its wait never stalls the matrix pipe
     if (kt + 2 < nchunks) {
-      write_chunk((kt + 2) & 3);
+      write_set(sA, (kt + 2) & 3);
       __syncthreads();
     }
-    wB[0] = wfragB[0];
-    wB[1] = wfragB[1];
+    wB[0] = sB.wfrag[0];
+    wB[1] = sB.wfrag[1];
   }
   if (nchunks & 1) {
     // odd count: last chunk sits in set A's buffer (written above)
@@ -482,9 +475,7 @@ void conv_fwd_kernel(const cvbf16* __restrict__ xpad,   // see VM note above
       for (int reg = 0; reg < 4; ++reg) {
         const int m = m0 + mi * 16 + kgrp * 4 + reg;
         if (m < M) {
-          float v = acc[mi][reg] + bv;
-          if (act == 1) v = fmaxf(v, 0.f);
-          else if (act == 2) v = fmaxf(v, 0.2f * v);
+          const float v = cv_bias_act(acc[mi][reg], bv, act);
           if (ostep == 1) {
             o[m] = cvf2b(v);
           } else {
@@ -493,6 +484,74 @@ void conv_fwd_kernel(const cvbf16* __restrict__ xpad,   // see VM note above
             o[(long long)oy * WOf + ox] = cvf2b(v);
           }
         }
+      }
+    }
+  }
+}
+
+// ---- pieces shared by the two direct LDS-halo kernels below. Each kernel
+// keeps what differs by design: its LDS swizzle (the aoff functor: byte
+// offset of pixel p, channel ci), its buffer count, its W panel addressing,
+// its choice among the halo-row writers, and its tap loop (see the note on
+// run_chunk in conv3x3_direct_kernel). ----
+
+// Halo row of NPX pixels from NPX/8 (rounded up) 16-byte loads at g, which
+// the caller has shown to lie inside the tensor; pixel xi of channel ci
+// goes to dst + aoff(p0 + xi, ci).
+template <int NPX, typename AOff>
+__device__ __forceinline__ void halo_row_vector(const cvbf16* __restrict__ g,
+                                                char* dst, int p0, int ci,
+                                                AOff aoff) {
+  constexpr int NV = (NPX + 7) / 8;
+  cv_u16x8 v[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j)
+    v[j] = *reinterpret_cast<const cv_u16x8*>(g + 8 * j);
+#pragma unroll
+  for (int xi = 0; xi < NPX; ++xi) {
+    unsigned short u = v[xi >> 3][xi & 7];
+    *reinterpret_cast<cvbf16*>(&dst[aoff(p0 + xi, ci)]) =
+        *reinterpret_cast<cvbf16*>(&u);
+  }
+}
+
+// The same row where the window may leave the tensor: columns cbase + xi
+// outside [0, Wp), and the whole row when !rowin, are staged as zeros.
+// rowb: offset of the (clamped) row's first element.
+template <int NPX, typename AOff>
+__device__ __forceinline__ void halo_row_border(const cvbf16* __restrict__ x,
+                                                long long rowb, bool rowin,
+                                                int cbase, int Wp, char* dst,
+                                                int p0, int ci, AOff aoff) {
+#pragma unroll
+  for (int xi = 0; xi < NPX; ++xi) {
+    const int col = cbase + xi;
+    unsigned short u =
+        cv_load_or_zero(x, rowb + min(max(col, 0), Wp - 1),
+                        rowin && (unsigned)col < (unsigned)Wp);
+    *reinterpret_cast<cvbf16*>(&dst[aoff(p0 + xi, ci)]) =
+        *reinterpret_cast<cvbf16*>(&u);
+  }
+}
+
+// Epilogue of an 8x8 output tile at (oy0, ox0): D rows are tile pixels,
+// row = mi*16 + kgrp*4 + reg; this lane's column is output channel ncol.
+__device__ __forceinline__ void direct_store_tile(
+    const cv_f32x4 (&acc)[4], const float* __restrict__ bias,
+    cvbf16* __restrict__ out_img, int ncol, int N, int kgrp, int oy0, int ox0,
+    int HO, int WO, int act) {
+  const float bv = (bias != nullptr && ncol < N) ? bias[ncol] : 0.f;
+  cvbf16* o = out_img + (long long)(ncol < N ? ncol : 0) * HO * WO;
+  if (ncol < N) {
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int m = mi * 16 + kgrp * 4 + reg;
+        const int oy = oy0 + (m >> 3), ox = ox0 + (m & 7);
+        if (oy < HO && ox < WO)
+          o[(long long)oy * WO + ox] =
+              cvf2b(cv_bias_act(acc[mi][reg], bv, act));
       }
     }
   }
@@ -509,11 +568,9 @@ void conv_fwd_kernel(const cvbf16* __restrict__ xpad,   // see VM note above
 // memory path, not LDS or the MFMAs, bounds this kernel (docs/KERNELS.md).
 //   out[n][oy0+py][ox0+px] = sum_{ci,r,s} xpad[ci][oy0+py+r][ox0+px+s]
 //                                        * w[n][(ci,r,s)]
-// vp: VIRTUAL symmetric pad — when nonzero, xpad is an UNPADDED tensor
-// (Hp, Wp are its real dims) and staging clamps/zero-masks the halo
-// window instead of reading a pre-padded buffer. Used where no other
-// consumer needs the padded buffer (backward-data dy; no-grad forwards),
-// killing the pad kernel + a full tensor round trip per conv.
+// vp >= 1: VIRTUAL symmetric pad. xpad is the UNPADDED tensor (Hp, Wp are
+// its real dims) and staging clamps/zero-masks the halo window: no pad
+// kernel and no padded copy of the tensor per conv.
 __global__ __launch_bounds__(256)
 void conv3x3_direct_kernel(const cvbf16* __restrict__ xpad, // (Ci, Hp, Wp)
                            const cvbf16* __restrict__ wmat, // (N, KP+AP)
@@ -561,75 +618,40 @@ void conv3x3_direct_kernel(const cvbf16* __restrict__ xpad, // (Ci, Hp, Wp)
     return p * (CIC * 2) + ((((ci >> 3) ^ (p & 7)) << 4) | ((ci & 7) << 1));
   };
 
-  typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
-  // stage chunk c's 10x10xCIC halo tile into LDS buffer buf.
-  // vp == 0 (pre-padded source): straight vector reads; the source buffer
-  // carries >= 16 elements of tail slack (ops/conv.py) so edge overshoot
-  // is safe. vp > 0: window row/cols outside [0,Hp)x[0,Wp) are zeroed; the
-  // vector path is used only when its 40-element read provably stays
-  // inside the tensor, else a per-element guarded path runs (first/last
-  // rows of the image, left/right border tiles).
-  // whole-tile interiority is uniform across the workgroup: interior tiles
-  // (the vast majority) take a straight-line vector-staging path identical
-  // in cost to the pre-padded vp==0 path; only border tiles pay the
-  // per-row clamp logic. +16 (not +10) on the column bound keeps the
-  // 16-element vector read inside the row.
-  const bool tile_int =
-      vp > 0 && oy0 >= vp && oy0 + 10 - vp <= Hp && ox0 >= vp &&
-      ox0 + 16 - vp <= Wp;
+  // stage chunk c's 10x10xCIC halo tile into LDS buffer buf; window rows
+  // and columns outside [0,Hp)x[0,Wp) are zeroed. Whole-tile interiority is
+  // uniform across the workgroup: interior tiles (the vast majority) take
+  // the straight-line vector path; +16 (not +10) on the column bound keeps
+  // the 16-element vector read inside the row. In the other tiles a row
+  // takes the vector path only when the read provably stays inside the
+  // tensor (40 elements from its end, conservatively), else the border
+  // path (first/last rows of the image, left/right border tiles).
+  const bool tile_int = oy0 >= vp && oy0 + 10 - vp <= Hp && ox0 >= vp &&
+                        ox0 + 16 - vp <= Wp;
   auto stage = [&](int c, int buf) {
     char* dst = As8 + buf * TB * 2;
     const long long nelem = (long long)Ci * Hp * Wp;
     for (int ridx = tid; ridx < CIC * 10; ridx += 256) {
       const int ci = ridx / 10, y = ridx % 10;
-      if (vp == 0 || tile_int) {
-        const int gy0 = oy0 - vp;  // >= 0 for tile_int; vp==0: plain base
-        const int yy = min(gy0 + y, Hp - 1);  // bottom edge tiles: clamped
-        const cvbf16* g =
-            x + ((long long)(c * CIC + ci) * Hp + yy) * Wp + (ox0 - vp);
-        const u16x8 a = *reinterpret_cast<const u16x8*>(g);
-        const u16x8 b = *reinterpret_cast<const u16x8*>(g + 8);
-#pragma unroll
-        for (int xi = 0; xi < 10; ++xi) {
-          unsigned short v = xi < 8 ? a[xi] : b[xi - 8];
-          *reinterpret_cast<cvbf16*>(&dst[aoff(y * XT + xi, ci)]) =
-              *reinterpret_cast<cvbf16*>(&v);
-        }
-        continue;
-      }
       const int gy = oy0 + y - vp;
       const int cbase = ox0 - vp;
+      if (tile_int) {
+        halo_row_vector<10>(
+            x + ((long long)(c * CIC + ci) * Hp + gy) * Wp + cbase, dst,
+            y * XT, ci, aoff);
+        continue;
+      }
       const bool rowin = gy >= 0 && gy < Hp;
       const long long rowb =
           ((long long)(c * CIC + ci) * Hp + (rowin ? gy : 0)) * Wp;
       const long long off = rowb + cbase;
-      if (rowin && cbase >= 0 && cbase + 10 <= Wp && off + 40 <= nelem) {
-        const cvbf16* g = x + off;
-        const u16x8 a = *reinterpret_cast<const u16x8*>(g);
-        const u16x8 b = *reinterpret_cast<const u16x8*>(g + 8);
-#pragma unroll
-        for (int xi = 0; xi < 10; ++xi) {
-          unsigned short v = xi < 8 ? a[xi] : b[xi - 8];
-          *reinterpret_cast<cvbf16*>(&dst[aoff(y * XT + xi, ci)]) =
-              *reinterpret_cast<cvbf16*>(&v);
-        }
-      } else {
-        // branchless border path: clamped unconditional loads + select
-        // (an if-guarded load per element serializes on vmcnt(0))
-#pragma unroll
-        for (int xi = 0; xi < 10; ++xi) {
-          const int col = cbase + xi;
-          const cvbf16 lv = x[rowb + min(max(col, 0), Wp - 1)];
-          const cvbf16 v =
-              (rowin && (unsigned)col < (unsigned)Wp) ? lv : cvf2b(0.f);
-          *reinterpret_cast<cvbf16*>(&dst[aoff(y * XT + xi, ci)]) = v;
-        }
-      }
+      if (rowin && cbase >= 0 && cbase + 10 <= Wp && off + 40 <= nelem)
+        halo_row_vector<10>(x + off, dst, y * XT, ci, aoff);
+      else
+        halo_row_border<10>(x, rowb, rowin, cbase, Wp, dst, y * XT, ci, aoff);
     }
   };
 
-  // my 16 output pixels per MFMA row-subtile: row l = mi*16 + colL
-  // -> pixel (py, px) = ((mi*16+colL) >> 3, (mi*16+colL) & 7)
   const int nchunks = Ci / CIC;
   // W prefetch: one 64-k tap group (2 MFMA k-steps) ahead — small register
   // sets (2 x 2 x b128) keep total pressure low enough for 3+ waves/SIMD
@@ -648,7 +670,12 @@ void conv3x3_direct_kernel(const cvbf16* __restrict__ xpad, // (Ci, Hp, Wp)
 
   // chunk body with COMPILE-TIME chunk parity: the W register-set rotation
   // (tap group index is 9c+tap, parity (c+tap)&1) must fold to direct
-  // register references — a runtime-selected pointer would spill both sets
+  // register references — a runtime-selected pointer would spill both sets.
+  // This loop and its twin in conv5x5s2_direct_kernel (tap count and pixel
+  // step differ) stay kernel-local lambdas on purpose: written as one shared
+  // function, hipcc merges the A-fragment reads that neighbouring taps have
+  // in common (144 -> 108 ds_read_b128) and keeps them in registers, 156 ->
+  // 212 VGPRs, a wave per SIMD less (profiles/r12_conv_device.md).
   auto run_chunk = [&](auto codd, int c) {
     constexpr int CO = decltype(codd)::value;
     const char* cur = As8 + CO * TB * 2;
@@ -689,26 +716,8 @@ void conv3x3_direct_kernel(const cvbf16* __restrict__ xpad, // (Ci, Hp, Wp)
     }
   }
 
-  // epilogue: D rows are tile pixels; row = mi*16 + kgrp*4 + reg
-  const float bv = (bias != nullptr && ncol < N) ? bias[ncol] : 0.f;
-  cvbf16* o = out + img * o_img_stride +
-              (long long)(ncol < N ? ncol : 0) * HO * WO;
-  if (ncol < N) {
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int m = mi * 16 + kgrp * 4 + reg;
-        const int oy = oy0 + (m >> 3), ox = ox0 + (m & 7);
-        if (oy < HO && ox < WO) {
-          float v = acc[mi][reg] + bv;
-          if (act == 1) v = fmaxf(v, 0.f);
-          else if (act == 2) v = fmaxf(v, 0.2f * v);
-          o[(long long)oy * WO + ox] = cvf2b(v);
-        }
-      }
-    }
-  }
+  direct_store_tile(acc, bias, out + img * o_img_stride, ncol, N, kgrp, oy0,
+                    ox0, HO, WO, act);
 }
 
 // Direct 5x5 stride-2 convolution (encoder h2 / to_bn shapes, Ci % 64 ==
@@ -760,7 +769,9 @@ void conv5x5s2_direct_kernel(const cvbf16* __restrict__ xpad, // (Ci, Hp, Wp)
     return p * (CIC * 2) + ((((ci >> 3) ^ key) << 4) | ((ci & 7) << 1));
   };
 
-  typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
+  // stage chunk c's 19x19xCIC halo tile: interior tiles by vector rows
+  // (+24 keeps the three 16-byte reads inside the row), the rest by border
+  // rows
   const int gy0 = 2 * oy0 - vp;
   const int cbase = 2 * ox0 - vp;
   const bool tile_int = gy0 >= 0 && gy0 + 19 <= Hp && cbase >= 0 &&
@@ -768,32 +779,16 @@ void conv5x5s2_direct_kernel(const cvbf16* __restrict__ xpad, // (Ci, Hp, Wp)
   auto stage = [&](int c) {
     for (int ridx = tid; ridx < CIC * 19; ridx += 256) {
       const int ci = ridx / 19, y = ridx % 19;
+      const int gy = gy0 + y;
       if (tile_int) {
-        const cvbf16* g =
-            x + ((long long)(c * CIC + ci) * Hp + (gy0 + y)) * Wp + cbase;
-        const u16x8 a = *reinterpret_cast<const u16x8*>(g);
-        const u16x8 b = *reinterpret_cast<const u16x8*>(g + 8);
-        const u16x8 e = *reinterpret_cast<const u16x8*>(g + 16);
-#pragma unroll
-        for (int xi = 0; xi < 19; ++xi) {
-          unsigned short v =
-              xi < 8 ? a[xi] : (xi < 16 ? b[xi - 8] : e[xi - 16]);
-          *reinterpret_cast<cvbf16*>(&As8[aoff(y * XT + xi, ci)]) =
-              *reinterpret_cast<cvbf16*>(&v);
-        }
-      } else {  // border: clamped unconditional loads + select
-        const int gy = gy0 + y;
+        halo_row_vector<19>(
+            x + ((long long)(c * CIC + ci) * Hp + gy) * Wp + cbase, As8,
+            y * XT, ci, aoff);
+      } else {
         const bool rowin = gy >= 0 && gy < Hp;
         const long long rowb =
             ((long long)(c * CIC + ci) * Hp + (rowin ? gy : 0)) * Wp;
-#pragma unroll
-        for (int xi = 0; xi < 19; ++xi) {
-          const int col = cbase + xi;
-          const cvbf16 lv = x[rowb + min(max(col, 0), Wp - 1)];
-          const cvbf16 v =
-              (rowin && (unsigned)col < (unsigned)Wp) ? lv : cvf2b(0.f);
-          *reinterpret_cast<cvbf16*>(&As8[aoff(y * XT + xi, ci)]) = v;
-        }
+        halo_row_border<19>(x, rowb, rowin, cbase, Wp, As8, y * XT, ci, aoff);
       }
     }
   };
@@ -811,6 +806,7 @@ void conv5x5s2_direct_kernel(const cvbf16* __restrict__ xpad, // (Ci, Hp, Wp)
   load_w(0, wA);
   __syncthreads();
 
+  // kernel-local like the 3x3 kernel's run_chunk, for the reason given there
   auto run_chunk = [&](auto codd, int c) {
     constexpr int CO = decltype(codd)::value;  // (c*25)&1 == c&1 (25 odd)
     const int kb = c * 25 * CIC;
@@ -848,25 +844,8 @@ void conv5x5s2_direct_kernel(const cvbf16* __restrict__ xpad, // (Ci, Hp, Wp)
     }
   }
 
-  const float bv = (bias != nullptr && ncol < N) ? bias[ncol] : 0.f;
-  cvbf16* o = out + img * o_img_stride +
-              (long long)(ncol < N ? ncol : 0) * HO * WO;
-  if (ncol < N) {
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int m = mi * 16 + kgrp * 4 + reg;
-        const int oy = oy0 + (m >> 3), ox = ox0 + (m & 7);
-        if (oy < HO && ox < WO) {
-          float v = acc[mi][reg] + bv;
-          if (act == 1) v = fmaxf(v, 0.f);
-          else if (act == 2) v = fmaxf(v, 0.2f * v);
-          o[(long long)oy * WO + ox] = cvf2b(v);
-        }
-      }
-    }
-  }
+  direct_store_tile(acc, bias, out + img * o_img_stride, ncol, N, kgrp, oy0,
+                    ox0, HO, WO, act);
 }
 
 // dW[co][k] += sum over the workgroup's pixel chunk of dy[co][m]*A[m][k].
@@ -881,7 +860,7 @@ void conv_wrw_kernel(const cvbf16* __restrict__ xpad,  // (Ci, Hp, Wp)
                      const int* __restrict__ koff,
                      int M, int N, int K,
                      long long x_img_stride, long long dy_img_stride,
-                     int pix_chunks, int WO, int mcontig,
+                     int pix_chunks, int WO,
                      int st, int vH, int vW, int vpt, int vpl) {
   // blockIdx.x: tap tile; blockIdx.y: cout tile; blockIdx.z: pixel chunk*img
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -965,16 +944,14 @@ void conv_wrw_kernel(const cvbf16* __restrict__ xpad,  // (Ci, Hp, Wp)
             const long long a =
                 ((long long)kci * vH + min(max(hv, 0), vH - 1)) * vW +
                 min(max(wv, 0), vW - 1);
-            const cvbf16 v = x[a];
-            sa[i] = ok ? *reinterpret_cast<const unsigned short*>(&v)
-                       : (unsigned short)0;
+            sa[i] = cv_load_or_zero(x, a, ok);
           }
         }
       } else {
 #pragma unroll
         for (int i = 0; i < 8; ++i) sa[i] = 0;
       }
-    } else if (inb && mcontig && ((p % WO) + 8 <= WO) && tap < K) {
+    } else if (inb && ((p % WO) + 8 <= WO) && tap < K) {
       sa = *reinterpret_cast<const u16x8*>(&x[mbase[p] + ko]);
     } else {
 #pragma unroll

@@ -232,9 +232,10 @@ def test_extension_has_the_named_conv_entry_points():
     mean something; the positional catch-alls are gone."""
     ext = _ext()
     for name in ("conv_direct", "conv_gather", "conv_flat", "conv_wrw_gather",
-                 "conv_wrw_flat", "conv_fwd_variant", "conv_wrw_variant"):
+                 "conv_wrw_flat", "conv_fwd_variant", "conv_wrw_variant",
+                 "pad_stuff_e4m3"):
         assert hasattr(ext, name), name
-    for name in ("conv_fwd", "conv_wrw"):
+    for name in ("conv_fwd", "conv_wrw", "pad_stuff"):
         assert not hasattr(ext, name), name
 
 

@@ -108,3 +108,23 @@ def test_weight_gradient(c, dev):
 @_params("conv3d")
 def test_conv3d_valid(c, dev):
     _check(c, dev, "conv3d")
+
+
+def test_entry_points_refuse_what_the_kernels_no_longer_stage(dev):
+    """The three calls whose staging paths are gone raise before anything
+    is launched: a direct 3x3 without a virtual pad, a bf16 flat gather at
+    stride 2, a bf16 flat weight gradient without contiguous pixel runs."""
+    from dsin_amd.ops import _require_ext
+    bf = dict(dtype=torch.bfloat16, device=dev)
+    x = torch.zeros(1, 64, 8, 8, **bf)
+    with pytest.raises(RuntimeError, match="virtual pad of at least 1"):
+        _require_ext("conv_direct")(x, torch.zeros(16, 64 * 9 + 8, **bf),
+                                    None, 16, 6, 6, 0, 0, 3)
+    tab = torch.zeros(9, dtype=torch.int32, device=dev)
+    x1 = torch.zeros(1, 1, 8, 8, **bf)
+    with pytest.raises(RuntimeError, match="stride 1 only"):
+        _require_ext("conv_flat")(x1, torch.zeros(1, 64 + 8, **bf), None, tab,
+                                  tab, 1, 9, 3, 3, 0, 2)
+    with pytest.raises(RuntimeError, match="needs mcontig"):
+        _require_ext("conv_wrw_flat")(x1, torch.zeros(1, 1, 3, 3, **bf), tab,
+                                      tab, 1, 9, 3, False)
