@@ -4,27 +4,9 @@
 // Semantics documented in ncc_search.hip (the host wrapper).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
+#include "device_common.h"
 
 namespace dsin {
-
-using ncbf16 = __hip_bfloat16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-
-__device__ __forceinline__ float nb2f(ncbf16 v) { return __bfloat162float(v); }
-__device__ __forceinline__ ncbf16 nf2b(float v) { return __float2bfloat16(v); }
-
-__device__ __forceinline__ unsigned int nfloat_flip(float f) {
-  unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float nwave_reduce_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
 
 // KITTI stats used inside the SI search (reference src/siFinder.py:62-63;
 // the `variances` there are standard deviations)
@@ -40,6 +22,12 @@ constexpr int NCC_TP = 32;   // patches per workgroup (MFMA 32x32 M tile)
 constexpr int NCC_TJ = 128;  // cols per workgroup (4 waves x 32)
 constexpr int NCC_TI = 8;    // rows looped per workgroup
 constexpr int NCC_APAD = 8;  // bf16 pad per A row for the b128 column reads
+// v2 only (ncc_main_v2_kernel):
+constexpr int NCC_SL = 384;  // taps per A slice (multiple of 16; 2x25KB buffers -> 3 blocks/CU)
+constexpr int NCC_TJ2 = 64;  // v2 col tile: 2 j-waves x 32 — the y window
+                             // (3 x 27 x 87 bf16 = 14 KB/block) then fits
+                             // L1 with two co-resident blocks; the other 2
+                             // waves take the other 4-row output group
 
 // ---------------------------------------------------------------- stage 0
 // Offset tables, computed once per call:
@@ -62,16 +50,16 @@ __global__ void ncc_offsets_kernel(unsigned int* __restrict__ aoffs,
 // ---------------------------------------------------------------- stage 1
 
 __global__ void transform_kernel(const float* __restrict__ img,
-                                 ncbf16* __restrict__ out, long long hw) {
+                                 bf16* __restrict__ out, long long hw) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long stride = (long long)gridDim.x * blockDim.x;
   for (; i < hw; i += stride) {
     float r = (img[i] - SIF_MEAN[0]) / SIF_STD[0];
     float g = (img[hw + i] - SIF_MEAN[1]) / SIF_STD[1];
     float b = (img[2 * hw + i] - SIF_MEAN[2]) / SIF_STD[2];
-    out[i] = nf2b(r + g);
-    out[hw + i] = nf2b(r - g);
-    out[2 * hw + i] = nf2b(0.5f * (r + b));
+    out[i] = f2b(r + g);
+    out[hw + i] = f2b(r - g);
+    out[2 * hw + i] = f2b(0.5f * (r + b));
   }
 }
 
@@ -91,7 +79,7 @@ __device__ __forceinline__ float lab_f(float t) {
 }
 
 __global__ void lab_transform_kernel(const float* __restrict__ img,
-                                     ncbf16* __restrict__ out, long long hw) {
+                                     bf16* __restrict__ out, long long hw) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long stride = (long long)gridDim.x * blockDim.x;
   for (; i < hw; i += stride) {
@@ -105,15 +93,15 @@ __global__ void lab_transform_kernel(const float* __restrict__ img,
     const float z = (0.019334f * r + 0.119193f * g + 0.950227f * b) *
                     (float)(1.0 / 1.088754);
     const float fx = lab_f(x), fy = lab_f(y), fz = lab_f(z);
-    out[i] = nf2b(116.f * fy - 16.f);
-    out[hw + i] = nf2b(500.f * (fx - fy));
-    out[2 * hw + i] = nf2b(200.f * (fy - fz));
+    out[i] = f2b(116.f * fy - 16.f);
+    out[hw + i] = f2b(500.f * (fx - fy));
+    out[2 * hw + i] = f2b(200.f * (fy - fz));
   }
 }
 
 // ---------------------------------------------------------------- stage 2
 
-__global__ void patch_stats_kernel(const ncbf16* __restrict__ tx,
+__global__ void patch_stats_kernel(const bf16* __restrict__ tx,
                                    const unsigned int* __restrict__ aoffs,
                                    float* __restrict__ psum,
                                    float* __restrict__ psum2,
@@ -123,12 +111,12 @@ __global__ void patch_stats_kernel(const ncbf16* __restrict__ tx,
   long long base = (long long)((p / gw) * ph) * W + (p % gw) * pw;
   float s = 0.f, s2 = 0.f;
   for (int k = threadIdx.x; k < K; k += blockDim.x) {
-    float v = nb2f(tx[base + aoffs[k]]);
+    float v = b2f(tx[base + aoffs[k]]);
     s += v;
     s2 += v * v;
   }
-  s = nwave_reduce_sum(s);
-  s2 = nwave_reduce_sum(s2);
+  s = wave_reduce_sum(s);
+  s2 = wave_reduce_sum(s2);
   if (threadIdx.x == 0) {
     psum[p] = s;
     psum2[p] = s2;
@@ -137,7 +125,7 @@ __global__ void patch_stats_kernel(const ncbf16* __restrict__ tx,
 
 // ---------------------------------------------------------------- stage 3
 
-__global__ void ysum_row_kernel(const ncbf16* __restrict__ ty,
+__global__ void ysum_row_kernel(const bf16* __restrict__ ty,
                                 float* __restrict__ s1, float* __restrict__ s2,
                                 int H, int W, int pw, int Wc) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -146,9 +134,9 @@ __global__ void ysum_row_kernel(const ncbf16* __restrict__ ty,
   int r = i / Wc, j = i % Wc;
   float a = 0.f, b = 0.f;
   for (int c = 0; c < 3; ++c) {
-    const ncbf16* row = ty + ((long long)c * H + r) * W + j;
+    const bf16* row = ty + ((long long)c * H + r) * W + j;
     for (int k = 0; k < pw; ++k) {
-      float v = nb2f(row[k]);
+      float v = b2f(row[k]);
       a += v;
       b += v * v;
     }
@@ -175,66 +163,69 @@ __global__ void ysum_col_kernel(const float* __restrict__ s1,
   sy2[i] = b;
 }
 
-// ---------------------------------------------------------------- stage 4
-// Main correlation kernel. MFMA 16x16x32 bf16; per k-chunk the B fragment is
-// gathered from the LDS y-window via the koffs table (1 broadcast b128 read
-// of 8 offsets + 8 u16 value reads per MFMA — no per-element index math).
-// Epilogue fully predicated (no divergent branches): fast rsqrt Pearson
-// normalization, inline Gaussian prior, packed (flipped-float | ~idx) u64
-// running max -> one atomicMax per patch at the end.
-//
-// L2 = true is the L2+LAB mode: same staging, MFMA loop and LDS layout; the
-// epilogue scores d = sum_x2 - 2*xy + sum_y2 (times the same prior) and the
-// winner is the MINIMUM, taken by the same atomicMax on the key of 0 - d
-// (the subtraction folds -0 into +0, so equal distances give one key and
-// the smallest index still wins). Pstat then holds sum_x2 in row 0 and the
-// two prior centres in rows 3 and 4; psum and sy are not read.
 
+// ------------------------------------------- stage 4: the shared pieces
+// Both main kernels run mfma_f32_32x32x16_bf16 with a patch tile as A:
+// A[row = l & 31][k = (l >> 5) * 8 + e], B[k][col = l & 31], and accumulator
+// register `reg` of lane l holds C[ncc_prow(reg, l >> 5)][l & 31].
+
+__device__ __forceinline__ int ncc_prow(int reg, int kgrp) {
+  return (reg & 3) + 8 * (reg >> 2) + 4 * kgrp;
+}
+
+// Dynamic LDS of the two main kernels: byte offsets of the arrays behind As
+// (which starts the block) and the launch's byte count. The kernels place
+// their arrays by these and the host wrapper sizes the launch by them.
+//   v1: As [TP][ASTRIDE] bf16 | Ys [3][YR][YCP] bf16 | Ko [KP] u16 | Pstat
+//   v2: As 2 x [TP][ASTRIDE] bf16 | Pstat
+// Pstat is [5][TP] float: per patch sum_x, mean_x, den_x (L2: sum_x2 in row
+// 0, rows 1 and 2 unused), then the prior's centre row and column.
+struct NccLdsV1 {
+  int KP, YR, YC, YCP, ASTRIDE;
+  int ys, ko, pstat;
+  size_t bytes;
+};
+struct NccLdsV2 {
+  int KP, ASTRIDE;
+  int pstat;
+  size_t bytes;
+};
+
+constexpr int NCC_PSTAT_BYTES = 5 * NCC_TP * 4;
+
+__host__ __device__ constexpr NccLdsV1 ncc_lds_v1(int ph, int pw) {
+  NccLdsV1 l{};
+  l.KP = (3 * ph * pw + 15) & ~15;
+  l.YR = NCC_TI + ph - 1;
+  l.YC = NCC_TJ + pw - 1;
+  l.YCP = (l.YC + 8) & ~7;
+  l.ASTRIDE = l.KP + NCC_APAD;
+  l.ys = NCC_TP * l.ASTRIDE * 2;
+  l.ko = l.ys + 3 * l.YR * l.YCP * 2;
+  l.pstat = l.ko + l.KP * 2;
+  l.bytes = (size_t)l.pstat + NCC_PSTAT_BYTES;
+  return l;
+}
+
+__host__ __device__ constexpr NccLdsV2 ncc_lds_v2(int ph, int pw) {
+  NccLdsV2 l{};
+  l.KP = (3 * ph * pw + 15) & ~15;
+  l.ASTRIDE = NCC_SL + NCC_APAD;
+  l.pstat = 2 * NCC_TP * l.ASTRIDE * 2;
+  l.bytes = (size_t)l.pstat + NCC_PSTAT_BYTES;
+  return l;
+}
+
+// The first NCC_TP threads of a workgroup fill Pstat for patches p0..p0+TP-1
+// (clamped to the last patch; rows beyond P are masked in the epilogue).
 template <bool L2>
-__global__ __launch_bounds__(256)
-void ncc_main_kernel(const ncbf16* __restrict__ tx, const ncbf16* __restrict__ ty,
-                     const unsigned int* __restrict__ aoffs,
-                     const unsigned short* __restrict__ koffs,
-                     const float* __restrict__ psum,
-                     const float* __restrict__ psum2,
-                     const float* __restrict__ sy,
-                     const float* __restrict__ sy2,
-                     unsigned long long* __restrict__ best,  // (P,)
-                     int H, int W, int ph, int pw, int gw, int P,
-                     int Hc, int Wc, int use_mask) {
-  // mfma_f32_32x32x16_bf16: A[row=l&31][k=(l>>5)*8+e], B[k][col=l&31],
-  // C row = (reg&3) + 8*(reg>>2) + 4*(l>>5). 2x the flops per B-gather of
-  // the 16x16 shape (the gather is the cost here). Two interleaved i-rows
-  // keep two independent accumulator chains in flight.
-  const int K = 3 * ph * pw;
-  const int KP = (K + 15) & ~15;
-  const int YR = NCC_TI + ph - 1;
-  const int YC = NCC_TJ + pw - 1;
-  const int YCP = (YC + 8) & ~7;
-  const int ASTRIDE = KP + NCC_APAD;
-
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  ncbf16* As = reinterpret_cast<ncbf16*>(smem);                // [TP][ASTRIDE]
-  ncbf16* Ys = As + NCC_TP * ASTRIDE;                          // [3][YR][YCP]
-  unsigned short* Ko = reinterpret_cast<unsigned short*>(Ys + 3 * YR * YCP);
-  float* Pstat = reinterpret_cast<float*>(Ko + ((KP + 7) & ~7));  // [5][TP]
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int j0 = blockIdx.x * NCC_TJ;
-  const int i0 = blockIdx.y * NCC_TI;
-  const int p0 = blockIdx.z * NCC_TP;
-
-  const float fK = (float)K;
-  const float invK = 1.f / fK;
-  const float ish2 = 4.0f / ((float)H * (float)H);   // 1/sh^2, sh = H/2
-  const float isw2 = 4.0f / ((float)W * (float)W);
-
-  // ---- stage A tile (32 patches x K), y window, koffs, patch stats ----
-  const int php_w = ph * pw;
-  for (int k = tid; k < KP; k += 256) Ko[k] = (k < K) ? koffs[k] : 0;
+__device__ __forceinline__ void ncc_stage_pstat(
+    float* __restrict__ Pstat, int tid, int p0, int P,
+    const float* __restrict__ psum, const float* __restrict__ psum2, int K,
+    int ph, int pw, int gw) {
   if (tid < NCC_TP) {
+    const float fK = (float)K;
+    const float invK = 1.f / fK;
     const int p = min(p0 + tid, P - 1);
     if constexpr (L2) {
       Pstat[tid] = psum2[p];
@@ -248,6 +239,138 @@ void ncc_main_kernel(const ncbf16* __restrict__ tx, const ncbf16* __restrict__ t
     Pstat[3 * NCC_TP + tid] = ((float)(p / gw) + 0.5f) * (float)ph;  // cr
     Pstat[4 * NCC_TP + tid] = ((float)(p % gw) + 0.5f) * (float)pw;  // cw
   }
+}
+
+// What the epilogue needs besides an accumulator: the call's geometry and
+// this lane's place in it (first patch of the workgroup, output column,
+// half-wave). Passed by value: by reference ncc_main_v2_kernel<false>
+// compiles to 184 registers instead of 180 and the v1 kernels to 16 more
+// (profiles/r13_ncc_device.md).
+struct NccEpi {
+  int H, W, ph, pw, P, Wc, K, use_mask;
+  int p0, j, kgrp;
+};
+
+// Scores output row iw of one accumulator (16 patches x this lane's column)
+// and folds them into the lane's running keys. Fully predicated, no divergent
+// branch: fast-rsqrt Pearson (or the L2 distance), the Gaussian prior
+// evaluated inline, then the key (flipped float << 32 | ~idx), so that the
+// u64 maximum is the best score at the smallest flat index. The L2 winner is
+// the MINIMUM, taken by the same maximum on the key of 0 - d: the
+// subtraction folds -0 into +0, so equal distances give one key.
+template <bool L2>
+__device__ __forceinline__ void ncc_epilogue_row(
+    const f32x16& acc, int iw, const NccEpi g,
+    const float* __restrict__ Pstat, const float* __restrict__ sy,
+    const float* __restrict__ sy2, unsigned long long (&bestk)[16]) {
+  const float fK = (float)g.K;
+  const float invK = 1.f / fK;
+  const float ish2 = 4.0f / ((float)g.H * (float)g.H);   // 1/sh^2, sh = H/2
+  const float isw2 = 4.0f / ((float)g.W * (float)g.W);
+  const bool jvalid = g.j < g.Wc;
+  const long long sidx = (long long)iw * g.Wc + (jvalid ? g.j : 0);
+  const float di = (float)(iw + g.ph / 2 - 1);
+  const float dj0 = (float)(g.j + g.pw / 2 - 1);
+  const unsigned int idx = (unsigned int)(iw * g.Wc + g.j);
+  const float sy2v = sy2[sidx];
+  float syv = 0.f, ym = 0.f, deny = 0.f;
+  if constexpr (!L2) {
+    syv = sy[sidx];
+    ym = syv * invK;
+    deny = sy2v - 2.f * ym * syv + fK * ym * ym;
+  }
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) {
+    const int prow = ncc_prow(reg, g.kgrp);
+    const float av = acc[reg];
+    float val;
+    if constexpr (L2) {
+      val = Pstat[prow] - 2.f * av + sy2v;
+    } else {
+      const float sxv = Pstat[prow];
+      const float xm = Pstat[NCC_TP + prow];
+      const float denx = Pstat[2 * NCC_TP + prow];
+      const float num = av - ym * sxv - xm * syv + fK * xm * ym;
+      val = num * __builtin_amdgcn_rsqf(fmaxf(denx * deny, NCC_EPS));
+    }
+    if (g.use_mask) {
+      const float dd = di - Pstat[3 * NCC_TP + prow];
+      const float dj = dj0 - Pstat[4 * NCC_TP + prow];
+      val *= __expf(-FOURLN2 * (dd * dd * ish2 + dj * dj * isw2));
+    }
+    unsigned long long key =
+        ((unsigned long long)float_flip(L2 ? 0.f - val : val) << 32) |
+        (unsigned long long)(~idx);
+    key = (jvalid && (g.p0 + prow) < g.P) ? key : 0ull;
+    if (key > bestk[reg]) bestk[reg] = key;
+  }
+}
+
+// Reduces the running keys across the 32 lanes of each half-wave (distinct
+// columns, the same 16 patches) and sends one atomicMax per patch.
+__device__ __forceinline__ void ncc_merge_best(
+    const unsigned long long (&bestk)[16],
+    unsigned long long* __restrict__ best, int p0, int P, int lane) {
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) {
+    unsigned long long k = bestk[reg];
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) {
+      unsigned long long other =
+          (unsigned long long)__shfl_xor((long long)k, off, 32);
+      if (other > k) k = other;
+    }
+    const int prow = p0 + ncc_prow(reg, lane >> 5);
+    if ((lane & 31) == 0 && prow < P && k != 0ull) atomicMax(&best[prow], k);
+  }
+}
+
+// ---------------------------------------------------------------- stage 4
+// Main correlation kernel, v1 (any pw). MFMA 32x32x16 bf16: 2x the flops per
+// B gather of the 16x16 shape, and the gather is the cost here. Per k-chunk
+// the B fragment is gathered from the LDS y-window via the koffs table (1
+// broadcast b128 read of 8 offsets + 8 u16 value reads per MFMA, no
+// per-element index math). Two interleaved i-rows keep two independent
+// accumulator chains in flight. Epilogue: ncc_epilogue_row per row, one
+// ncc_merge_best at the end.
+//
+// L2 = true is the L2+LAB mode: same staging, MFMA loop and LDS layout; only
+// the epilogue's score and the contents of Pstat differ; psum and sy are not
+// read.
+
+template <bool L2>
+__global__ __launch_bounds__(256)
+void ncc_main_kernel(const bf16* __restrict__ tx, const bf16* __restrict__ ty,
+                     const unsigned int* __restrict__ aoffs,
+                     const unsigned short* __restrict__ koffs,
+                     const float* __restrict__ psum,
+                     const float* __restrict__ psum2,
+                     const float* __restrict__ sy,
+                     const float* __restrict__ sy2,
+                     unsigned long long* __restrict__ best,  // (P,)
+                     int H, int W, int ph, int pw, int gw, int P,
+                     int Hc, int Wc, int use_mask) {
+  const int K = 3 * ph * pw;
+  const NccLdsV1 lds = ncc_lds_v1(ph, pw);
+  const int KP = lds.KP, YR = lds.YR, YC = lds.YC, YCP = lds.YCP;
+  const int ASTRIDE = lds.ASTRIDE;
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bf16* As = reinterpret_cast<bf16*>(smem);                  // [TP][ASTRIDE]
+  bf16* Ys = reinterpret_cast<bf16*>(smem + lds.ys);         // [3][YR][YCP]
+  unsigned short* Ko = reinterpret_cast<unsigned short*>(smem + lds.ko);
+  float* Pstat = reinterpret_cast<float*>(smem + lds.pstat);  // [5][TP]
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int j0 = blockIdx.x * NCC_TJ;
+  const int i0 = blockIdx.y * NCC_TI;
+  const int p0 = blockIdx.z * NCC_TP;
+
+  // ---- stage A tile (32 patches x K), y window, koffs, patch stats ----
+  for (int k = tid; k < KP; k += 256) Ko[k] = (k < K) ? koffs[k] : 0;
+  ncc_stage_pstat<L2>(Pstat, tid, p0, P, psum, psum2, K, ph, pw, gw);
 #pragma unroll 1
   for (int pi = 0; pi < NCC_TP; ++pi) {
     const int p = p0 + pi;
@@ -255,7 +378,7 @@ void ncc_main_kernel(const ncbf16* __restrict__ tx, const ncbf16* __restrict__ t
         (p < P) ? (long long)((p / gw) * ph) * W + (long long)((p % gw) * pw)
                 : 0;
     for (int k = tid; k < KP; k += 256) {
-      ncbf16 v = nf2b(0.f);
+      bf16 v = f2b(0.f);
       if (k < K && p < P) v = tx[pbase + aoffs[k]];
       As[pi * ASTRIDE + k] = v;
     }
@@ -267,9 +390,9 @@ void ncc_main_kernel(const ncbf16* __restrict__ tx, const ncbf16* __restrict__ t
       int rr = rem / YC, cc = rem % YC;
       int r = i0 + rr, col = j0 + cc;
       float v = (r < H && col < W)
-                    ? nb2f(ty[((long long)c * H + r) * W + col])
+                    ? b2f(ty[((long long)c * H + r) * W + col])
                     : 0.f;
-      Ys[(c * YR + rr) * YCP + cc] = nf2b(v);
+      Ys[(c * YR + rr) * YCP + cc] = f2b(v);
     }
   }
   __syncthreads();
@@ -277,17 +400,14 @@ void ncc_main_kernel(const ncbf16* __restrict__ tx, const ncbf16* __restrict__ t
   const int colL = lane & 31;          // col within the wave's 32
   const int kgrp = lane >> 5;          // 0/1 (k-offset 0/8 within 16)
   const int jj = wid * 32 + colL;
-  const int j = j0 + jj;
-  const bool jvalid = j < Wc;
+  const NccEpi epi = {H, W, ph, pw, P, Wc, K, use_mask, p0, j0 + jj, kgrp};
 
-  typedef __attribute__((ext_vector_type(16))) float f32x16;
   unsigned long long bestk[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) bestk[r] = 0ull;
 
-  const ncbf16* __restrict__ arow = &As[kgrp * 8];
+  const bf16* __restrict__ arow = &As[kgrp * 8];
   const unsigned short* __restrict__ krow = &Ko[kgrp * 8];
-  typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
 
   for (int i = 0; i < NCC_TI; i += 2) {
     const int ii = i0 + i;
@@ -295,16 +415,16 @@ void ncc_main_kernel(const ncbf16* __restrict__ tx, const ncbf16* __restrict__ t
     const bool i1ok = (ii + 1) < Hc;
     f32x16 acc0 = {};
     f32x16 acc1 = {};
-    const ncbf16* __restrict__ yb0 = &Ys[i * YCP + jj];
-    const ncbf16* __restrict__ yb1 = &Ys[(i + 1) * YCP + jj];
+    const bf16* __restrict__ yb0 = &Ys[i * YCP + jj];
+    const bf16* __restrict__ yb1 = &Ys[(i + 1) * YCP + jj];
     for (int kt = 0; kt < KP / 16; ++kt) {
       const u16x8 ko8 =
           *reinterpret_cast<const u16x8*>(krow + kt * 16);
       bf16x8 bf0, bf1;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        ncbf16 v0 = yb0[ko8[e]];
-        ncbf16 v1 = yb1[ko8[e]];
+        bf16 v0 = yb0[ko8[e]];
+        bf16 v1 = yb1[ko8[e]];
         bf0[e] = *reinterpret_cast<__bf16*>(&v0);
         bf1[e] = *reinterpret_cast<__bf16*>(&v1);
       }
@@ -314,77 +434,10 @@ void ncc_main_kernel(const ncbf16* __restrict__ tx, const ncbf16* __restrict__ t
       acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afrag, bf0, acc0, 0, 0, 0);
       acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afrag, bf1, acc1, 0, 0, 0);
     }
-    // ---- epilogue for rows ii and ii+1 ----
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      if (half == 1 && !i1ok) break;
-      const int iw = ii + half;
-      const long long sidx = (long long)iw * Wc + (jvalid ? j : 0);
-      const float di = (float)(iw + ph / 2 - 1);
-      const unsigned int idx = (unsigned int)(iw * Wc + j);
-      if constexpr (L2) {
-        const float sy2v = sy2[sidx];
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-          const int prow = (reg & 3) + 8 * (reg >> 2) + 4 * kgrp;
-          const float av = half == 0 ? acc0[reg] : acc1[reg];
-          float val = Pstat[prow] - 2.f * av + sy2v;
-          if (use_mask) {
-            const float dd = di - Pstat[3 * NCC_TP + prow];
-            const float dj =
-                (float)(j + pw / 2 - 1) - Pstat[4 * NCC_TP + prow];
-            val *= __expf(-FOURLN2 * (dd * dd * ish2 + dj * dj * isw2));
-          }
-          unsigned long long key =
-              ((unsigned long long)nfloat_flip(0.f - val) << 32) |
-              (unsigned long long)(~idx);
-          key = (jvalid && (p0 + prow) < P) ? key : 0ull;
-          if (key > bestk[reg]) bestk[reg] = key;
-        }
-      } else {
-        const float syv = sy[sidx];
-        const float sy2v = sy2[sidx];
-        const float ym = syv * invK;
-        const float deny = sy2v - 2.f * ym * syv + fK * ym * ym;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-          const int prow = (reg & 3) + 8 * (reg >> 2) + 4 * kgrp;
-          const float av = half == 0 ? acc0[reg] : acc1[reg];
-          const float sxv = Pstat[prow];
-          const float xm = Pstat[NCC_TP + prow];
-          const float denx = Pstat[2 * NCC_TP + prow];
-          const float num = av - ym * sxv - xm * syv + fK * xm * ym;
-          float val =
-              num * __builtin_amdgcn_rsqf(fmaxf(denx * deny, NCC_EPS));
-          if (use_mask) {
-            const float dd = di - Pstat[3 * NCC_TP + prow];
-            const float dj =
-                (float)(j + pw / 2 - 1) - Pstat[4 * NCC_TP + prow];
-            val *= __expf(-FOURLN2 * (dd * dd * ish2 + dj * dj * isw2));
-          }
-          unsigned long long key =
-              ((unsigned long long)nfloat_flip(val) << 32) |
-              (unsigned long long)(~idx);
-          key = (jvalid && (p0 + prow) < P) ? key : 0ull;
-          if (key > bestk[reg]) bestk[reg] = key;
-        }
-      }
-    }
+    ncc_epilogue_row<L2>(acc0, ii, epi, Pstat, sy, sy2, bestk);
+    if (i1ok) ncc_epilogue_row<L2>(acc1, ii + 1, epi, Pstat, sy, sy2, bestk);
   }
-
-  // reduce across the 32 lanes of each half (distinct cols, same row set)
-#pragma unroll
-  for (int reg = 0; reg < 16; ++reg) {
-    unsigned long long k = bestk[reg];
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) {
-      unsigned long long other =
-          (unsigned long long)__shfl_xor((long long)k, off, 32);
-      if (other > k) k = other;
-    }
-    const int prow = p0 + (reg & 3) + 8 * (reg >> 2) + 4 * kgrp;
-    if (colL == 0 && prow < P && k != 0ull) atomicMax(&best[prow], k);
-  }
+  ncc_merge_best(bestk, best, p0, P, lane);
 }
 
 // ------------------------------------------------------- stage 4, variant 2
@@ -400,17 +453,12 @@ void ncc_main_kernel(const ncbf16* __restrict__ tx, const ncbf16* __restrict__ t
 //     packing VALU);
 //   * the k-loop is OUTER over 4-row output groups, so one LDS A fragment
 //     feeds 4 MFMAs (4 independent accumulator chains).
-constexpr int NCC_SL = 384;  // taps per A slice (multiple of 16; 2x25KB buffers -> 3 blocks/CU)
-constexpr int NCC_TJ2 = 64;  // v2 col tile: 2 j-waves x 32 — the y window
-                             // (3 x 27 x 87 bf16 = 14 KB/block) then fits
-                             // L1 with two co-resident blocks; the other 2
-                             // waves take the other 4-row output group
 
-// L2 = true: the L2+LAB epilogue and Pstat contents of ncc_main_kernel<true>
+// Same Pstat, epilogue and merge as v1, in both modes.
 template <bool L2>
 __global__ __launch_bounds__(256)
-void ncc_main_v2_kernel(const ncbf16* __restrict__ tx,
-                        const ncbf16* __restrict__ ty,
+void ncc_main_v2_kernel(const bf16* __restrict__ tx,
+                        const bf16* __restrict__ ty,
                         const unsigned int* __restrict__ aoffs,
                         const float* __restrict__ psum,
                         const float* __restrict__ psum2,
@@ -420,12 +468,13 @@ void ncc_main_v2_kernel(const ncbf16* __restrict__ tx,
                         int H, int W, int ph, int pw, int gw, int P,
                         int Hc, int Wc, int use_mask) {
   const int K = 3 * ph * pw;
-  const int KP = (K + 15) & ~15;
-  const int ASTRIDE = NCC_SL + NCC_APAD;
+  const NccLdsV2 lds = ncc_lds_v2(ph, pw);
+  const int KP = lds.KP;
+  const int ASTRIDE = lds.ASTRIDE;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  ncbf16* As = reinterpret_cast<ncbf16*>(smem);      // 2 x [TP][ASTRIDE]
-  float* Pstat = reinterpret_cast<float*>(As + 2 * NCC_TP * ASTRIDE);  // [5][TP]
+  bf16* As = reinterpret_cast<bf16*>(smem);                   // 2 x [TP][ASTRIDE]
+  float* Pstat = reinterpret_cast<float*>(smem + lds.pstat);  // [5][TP]
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -434,25 +483,7 @@ void ncc_main_v2_kernel(const ncbf16* __restrict__ tx,
   const int i0 = blockIdx.y * NCC_TI;
   const int p0 = blockIdx.z * NCC_TP;
 
-  const float fK = (float)K;
-  const float invK = 1.f / fK;
-  const float ish2 = 4.0f / ((float)H * (float)H);
-  const float isw2 = 4.0f / ((float)W * (float)W);
-
-  if (tid < NCC_TP) {
-    const int p = min(p0 + tid, P - 1);
-    if constexpr (L2) {
-      Pstat[tid] = psum2[p];
-    } else {
-      const float sxv = psum[p];
-      const float xm = sxv * invK;
-      Pstat[tid] = sxv;
-      Pstat[NCC_TP + tid] = xm;
-      Pstat[2 * NCC_TP + tid] = psum2[p] - 2.f * xm * sxv + fK * xm * xm;
-    }
-    Pstat[3 * NCC_TP + tid] = ((float)(p / gw) + 0.5f) * (float)ph;
-    Pstat[4 * NCC_TP + tid] = ((float)(p % gw) + 0.5f) * (float)pw;
-  }
+  ncc_stage_pstat<L2>(Pstat, tid, p0, P, psum, psum2, K, ph, pw, gw);
 
   // slice staging: 8 threads per patch row, each stages NCC_SL/8 taps (runs
   // of 8 contiguous image elements via aoffs); zero-fills beyond K / beyond
@@ -467,9 +498,8 @@ void ncc_main_v2_kernel(const ncbf16* __restrict__ tx,
   const long long s_pbase =
       s_pok ? (long long)((sp / gw) * ph) * W + (long long)((sp % gw) * pw)
             : 0;
-  typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
   auto stage_slice = [&](int s0, int buf) {
-    ncbf16* dst = As + buf * NCC_TP * ASTRIDE;
+    bf16* dst = As + buf * NCC_TP * ASTRIDE;
 #pragma unroll
     for (int r8 = 0; r8 < S_TAPS / 8; ++r8) {
       const int kl = s_k0 + r8 * 8;
@@ -485,65 +515,13 @@ void ncc_main_v2_kernel(const ncbf16* __restrict__ tx,
   const int kgrp = lane >> 5;
   const int jj = (wid & 1) * 32 + colL;   // 2 j-waves cover TJ2 columns
   const int g0 = (wid >> 1) * 4;          // 2 row-group waves cover TI rows
-  const int j = j0 + jj;
-  const bool jvalid = j < Wc;
+  const NccEpi epi = {H, W, ph, pw, P, Wc, K, use_mask, p0, j0 + jj, kgrp};
 
-  typedef __attribute__((ext_vector_type(16))) float f32x16;
   unsigned long long bestk[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) bestk[r] = 0ull;
 
   const int nslices = (KP + NCC_SL - 1) / NCC_SL;
-
-  // per-row epilogue (identical math to the v1 kernel)
-  auto epilogue_row = [&](const f32x16& acc, int iw) {
-    const long long sidx = (long long)iw * Wc + (jvalid ? j : 0);
-    const float di = (float)(iw + ph / 2 - 1);
-    const unsigned int idx = (unsigned int)(iw * Wc + j);
-    if constexpr (L2) {
-      const float sy2v = sy2[sidx];
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int prow = (reg & 3) + 8 * (reg >> 2) + 4 * kgrp;
-        float val = Pstat[prow] - 2.f * acc[reg] + sy2v;
-        if (use_mask) {
-          const float dd = di - Pstat[3 * NCC_TP + prow];
-          const float dj = (float)(j + pw / 2 - 1) - Pstat[4 * NCC_TP + prow];
-          val *= __expf(-FOURLN2 * (dd * dd * ish2 + dj * dj * isw2));
-        }
-        unsigned long long key =
-            ((unsigned long long)nfloat_flip(0.f - val) << 32) |
-            (unsigned long long)(~idx);
-        key = (jvalid && (p0 + prow) < P) ? key : 0ull;
-        if (key > bestk[reg]) bestk[reg] = key;
-      }
-    } else {
-      const float syv = sy[sidx];
-      const float sy2v = sy2[sidx];
-      const float ym = syv * invK;
-      const float deny = sy2v - 2.f * ym * syv + fK * ym * ym;
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int prow = (reg & 3) + 8 * (reg >> 2) + 4 * kgrp;
-        const float av = acc[reg];
-        const float sxv = Pstat[prow];
-        const float xm = Pstat[NCC_TP + prow];
-        const float denx = Pstat[2 * NCC_TP + prow];
-        const float num = av - ym * sxv - xm * syv + fK * xm * ym;
-        float val = num * __builtin_amdgcn_rsqf(fmaxf(denx * deny, NCC_EPS));
-        if (use_mask) {
-          const float dd = di - Pstat[3 * NCC_TP + prow];
-          const float dj = (float)(j + pw / 2 - 1) - Pstat[4 * NCC_TP + prow];
-          val *= __expf(-FOURLN2 * (dd * dd * ish2 + dj * dj * isw2));
-        }
-        unsigned long long key =
-            ((unsigned long long)nfloat_flip(val) << 32) |
-            (unsigned long long)(~idx);
-        key = (jvalid && (p0 + prow) < P) ? key : 0ull;
-        if (key > bestk[reg]) bestk[reg] = key;
-      }
-    }
-  };
 
   // this wave's 4-row output group (the A slices are shared by all waves)
   const int iig = i0 + g0;
@@ -561,7 +539,7 @@ void ncc_main_v2_kernel(const ncbf16* __restrict__ tx,
 #pragma unroll 1
   for (int s = 0; s < nslices; ++s) {
     if (s + 1 < nslices) stage_slice((s + 1) * NCC_SL, (s + 1) & 1);
-    ncbf16* As_cur = As + (s & 1) * NCC_TP * ASTRIDE;
+    bf16* As_cur = As + (s & 1) * NCC_TP * ASTRIDE;
     // incremental (c, a, b) decode of this half-wave's k-group
     int dyc, dya, dyb;
     {
@@ -621,33 +599,22 @@ void ncc_main_v2_kernel(const ncbf16* __restrict__ tx,
     if (kt < nkt) mfma_set(v0a, v1a, v2a, v3a, afa);  // odd tail
     __syncthreads();  // next slice's buffer fully written AND consumed
   }
-  if (iig + 0 < Hc) epilogue_row(a0, iig + 0);
-  if (iig + 1 < Hc) epilogue_row(a1, iig + 1);
-  if (iig + 2 < Hc) epilogue_row(a2, iig + 2);
-  if (iig + 3 < Hc) epilogue_row(a3, iig + 3);
+  if (iig + 0 < Hc) ncc_epilogue_row<L2>(a0, iig + 0, epi, Pstat, sy, sy2, bestk);
+  if (iig + 1 < Hc) ncc_epilogue_row<L2>(a1, iig + 1, epi, Pstat, sy, sy2, bestk);
+  if (iig + 2 < Hc) ncc_epilogue_row<L2>(a2, iig + 2, epi, Pstat, sy, sy2, bestk);
+  if (iig + 3 < Hc) ncc_epilogue_row<L2>(a3, iig + 3, epi, Pstat, sy, sy2, bestk);
 
-#pragma unroll
-  for (int reg = 0; reg < 16; ++reg) {
-    unsigned long long k = bestk[reg];
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) {
-      unsigned long long other =
-          (unsigned long long)__shfl_xor((long long)k, off, 32);
-      if (other > k) k = other;
-    }
-    const int prow = p0 + (reg & 3) + 8 * (reg >> 2) + 4 * kgrp;
-    if (colL == 0 && prow < P && k != 0ull) atomicMax(&best[prow], k);
-  }
+  ncc_merge_best(bestk, best, p0, P, lane);
 }
 
 // the four instantiations the host wrapper launches (also what a standalone
 // compile of this file emits)
 #define NCC_MAIN_ARGS                                                        \
-  const ncbf16*, const ncbf16*, const unsigned int*, const unsigned short*, \
+  const bf16*, const bf16*, const unsigned int*, const unsigned short*, \
       const float*, const float*, const float*, const float*,               \
       unsigned long long*, int, int, int, int, int, int, int, int, int
 #define NCC_MAIN_V2_ARGS                                                   \
-  const ncbf16*, const ncbf16*, const unsigned int*, const float*,        \
+  const bf16*, const bf16*, const unsigned int*, const float*,        \
       const float*, const float*, const float*, unsigned long long*, int, \
       int, int, int, int, int, int, int, int
 template __global__ void ncc_main_kernel<false>(NCC_MAIN_ARGS);

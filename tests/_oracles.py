@@ -39,7 +39,8 @@ NCC_FLOOR = 1e-5  # 1-ulp rsq and __expf of the epilogue on |score| <= 1,
 
 
 def ncc_v1_lds_bytes(ph, pw):
-    """Dynamic LDS of ncc_main_kernel, the formula of ncc_search.hip."""
+    """Dynamic LDS of ncc_main_kernel, the formula of ncc_lds_v1 in
+    ncc_kernels.h, written out again."""
     tp, tj, ti, apad = 32, 128, 8, 8
     k = 3 * ph * pw
     kp = (k + 15) & ~15
@@ -146,6 +147,19 @@ def ncc_tie_case(ty, tx, ny, nx, seed=0):
     g = torch.Generator().manual_seed(1000 + seed)
     block = torch.rand(3, ty, tx, generator=g) * 255
     return block.repeat(1, ny, nx).contiguous()
+
+
+def ncc_check_gather(y_syn, rows, cols, y_orig, ph, pw):
+    """Range of the locations, and y_syn == the y_orig windows bit for bit."""
+    _, h, w = y_orig.shape
+    assert rows.dtype == torch.int64 and cols.dtype == torch.int64
+    assert int(rows.min()) >= 0 and int(rows.max()) <= h - ph
+    assert int(cols.min()) >= 0 and int(cols.max()) <= w - pw
+    gw = w // pw
+    for p, (r0, c0) in enumerate(zip(rows.tolist(), cols.tolist())):
+        gr, gc = divmod(p, gw)
+        got = y_syn[:, gr * ph:(gr + 1) * ph, gc * pw:(gc + 1) * pw]
+        assert torch.equal(got, y_orig[:, r0:r0 + ph, c0:c0 + pw]), p
 
 
 # ------------------------------------------------------------ batch norm

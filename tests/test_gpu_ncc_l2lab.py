@@ -38,19 +38,6 @@ def _search(x, y_dec, y_orig, ph, pw, use_mask, dev):
     return y_syn.cpu(), rows.cpu(), cols.cpu()
 
 
-def _check_gather(y_syn, rows, cols, y_orig, ph, pw):
-    """Range of the locations, and y_syn == the y_orig windows bit for bit."""
-    _, h, w = y_orig.shape
-    assert rows.dtype == torch.int64 and cols.dtype == torch.int64
-    assert int(rows.min()) >= 0 and int(rows.max()) <= h - ph
-    assert int(cols.min()) >= 0 and int(cols.max()) <= w - pw
-    gw = w // pw
-    for p, (r0, c0) in enumerate(zip(rows.tolist(), cols.tolist())):
-        gr, gc = divmod(p, gw)
-        got = y_syn[:, gr * ph:(gr + 1) * ph, gc * pw:(gc + 1) * pw]
-        assert torch.equal(got, y_orig[:, r0:r0 + ph, c0:c0 + pw]), p
-
-
 # ------------------------------------------------------------ 1. transform
 
 def _transform_input():
@@ -102,7 +89,7 @@ def test_l2lab_search_against_oracle(dev, case):
     ty = ops.ncc_lab_transform(y_dec.to(dev)).cpu()
     d = L.l2_decide(tx, ty, ph, pw, use_mask)
     y_syn, rows, cols = _search(x, y_dec, y_orig, ph, pw, use_mask, dev)
-    _check_gather(y_syn, rows, cols, y_orig, ph, pw)
+    O.ncc_check_gather(y_syn, rows, cols, y_orig, ph, pw)
     L.l2_check(d, rows, cols, str(case))
     _, r32, c32 = ref.ncc_search_ref(x, y_dec, y_orig, ph, pw, use_mask,
                                      l2lab=True)
