@@ -74,18 +74,22 @@ void adam_step(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                torch::Tensor v, torch::Tensor lr, torch::Tensor step,
                c10::optional<torch::Tensor> wd, double b1, double b2,
                double eps) {
-  CHECK_CUDA_CONTIG(p);
-  CHECK_CUDA_CONTIG(g);
-  CHECK_CUDA_CONTIG(m);
-  CHECK_CUDA_CONTIG(v);
+  check_arg(p, "adam_step: p", torch::kFloat32);
   int64_t n = p.numel();
-  int grid = (int)std::min<int64_t>((n / 4 + 255) / 256, 2048);
+  check_arg_numel(g, "adam_step: g", torch::kFloat32, n);
+  check_arg_numel(m, "adam_step: m", torch::kFloat32, n);
+  check_arg_numel(v, "adam_step: v", torch::kFloat32, n);
+  check_arg_numel(lr, "adam_step: lr", torch::kFloat32, 1);
+  check_arg_numel(step, "adam_step: step", torch::kInt32, 1);
   const float* wdp = nullptr;
   if (wd.has_value()) {
-    CHECK_CUDA_CONTIG(wd.value());
+    check_arg_numel(*wd, "adam_step: wd", torch::kFloat32, n);
     wdp = wd->data_ptr<float>();
   }
-  hipLaunchKernelGGL(adam_step_kernel, dim3(std::max(grid, 1)), dim3(256), 0,
+  // four elements per thread
+  const int grid = ew_grid(n / 4, 2048);
+  hipLaunchKernelGGL(adam_step_kernel, dim3(std::max(grid, 1)),
+                     dim3(BLOCK_THREADS), 0,
                      at::cuda::getCurrentCUDAStream(), p.data_ptr<float>(),
                      g.data_ptr<float>(), m.data_ptr<float>(),
                      v.data_ptr<float>(), lr.data_ptr<float>(),

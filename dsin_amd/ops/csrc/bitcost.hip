@@ -60,38 +60,46 @@ __global__ void bitcost_ce_bwd_kernel(const float* __restrict__ g,
   }
 }
 
-torch::Tensor bitcost_ce_fwd(torch::Tensor logits, torch::Tensor symbols) {
-  CHECK_CUDA_CONTIG(logits);
-  CHECK_CUDA_CONTIG(symbols);
+// the checks both directions make: fp32 (N, L, C, H, W) logits of at most
+// MAX_LOGITS classes and one int64 symbol per site
+struct BitcostGeom {
+  int L;
+  int64_t S, total;  // sites per image, sites
+};
+
+static BitcostGeom bitcost_geom(const std::string& op,
+                                const torch::Tensor& logits,
+                                const torch::Tensor& symbols) {
+  check_arg(logits, (op + ": logits").c_str(), torch::kFloat32);
   TORCH_CHECK(logits.dim() == 5, "logits must be (N, L, C, H, W)");
-  TORCH_CHECK(logits.scalar_type() == torch::kFloat32, "logits must be fp32");
   int64_t N = logits.size(0), L = logits.size(1);
   TORCH_CHECK(L <= MAX_LOGITS, "at most ", MAX_LOGITS, " logit classes");
   int64_t S = logits.numel() / (N * L);
+  check_arg(symbols, (op + ": symbols").c_str(), torch::kInt64);
   TORCH_CHECK(symbols.numel() == N * S, "symbols shape mismatch");
+  return {(int)L, S, N * S};
+}
+
+torch::Tensor bitcost_ce_fwd(torch::Tensor logits, torch::Tensor symbols) {
+  const BitcostGeom q = bitcost_geom("bitcost_ce_fwd", logits, symbols);
   auto bits = torch::empty(symbols.sizes(), logits.options());
-  int64_t total = N * S;
-  int block = 256;
-  int grid = std::min<int64_t>((total + block - 1) / block, 4096);
-  hipLaunchKernelGGL(bitcost_ce_fwd_kernel, dim3(grid), dim3(block), 0,
+  hipLaunchKernelGGL(bitcost_ce_fwd_kernel, dim3(ew_grid(q.total)),
+                     dim3(BLOCK_THREADS), 0,
                      at::cuda::getCurrentCUDAStream(),
                      logits.data_ptr<float>(), symbols.data_ptr<int64_t>(),
-                     bits.data_ptr<float>(), (int)L, S, total);
+                     bits.data_ptr<float>(), q.L, q.S, q.total);
   return bits;
 }
 
 torch::Tensor bitcost_ce_bwd(torch::Tensor g, torch::Tensor logits,
                              torch::Tensor symbols) {
-  CHECK_CUDA_CONTIG(g);
-  CHECK_CUDA_CONTIG(logits);
-  CHECK_CUDA_CONTIG(symbols);
-  int64_t N = logits.size(0), L = logits.size(1);
-  int64_t S = logits.numel() / (N * L);
+  const BitcostGeom q = bitcost_geom("bitcost_ce_bwd", logits, symbols);
+  check_arg_numel(g, "bitcost_ce_bwd: g", torch::kFloat32, q.total);
   auto glogits = torch::empty_like(logits);
-  int64_t total = N * S;
-  int block = 256;
-  int grid = std::min<int64_t>((total + block - 1) / block, 4096);
-  hipLaunchKernelGGL(bitcost_ce_bwd_kernel, dim3(grid), dim3(block), 0,
+  const int L = q.L;
+  const int64_t S = q.S, total = q.total;
+  hipLaunchKernelGGL(bitcost_ce_bwd_kernel, dim3(ew_grid(total)),
+                     dim3(BLOCK_THREADS), 0,
                      at::cuda::getCurrentCUDAStream(),
                      g.data_ptr<float>(), logits.data_ptr<float>(),
                      symbols.data_ptr<int64_t>(), glogits.data_ptr<float>(),

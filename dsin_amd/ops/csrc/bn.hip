@@ -12,70 +12,79 @@
 //  bn_apply:       out = act(scale*y + shift)
 //  bn_bwd_part:    per-channel sum(dy_eff), sum(dy_eff*xhat), act' inline
 //  bn_bwd_apply:   dx = gamma*rstd*(dy_eff - s1/n - xhat*s2/n)
+//
+// Each kernel walks its row in 8-wide vectors and lets the first block take
+// the HW % 8 tail one element per thread; the per-element arithmetic of both
+// is one of the four bn_* functions below.
 
 #include "common.h"
 
 namespace dsin {
 
-using bnbf16 = __hip_bfloat16;
-typedef __attribute__((ext_vector_type(8))) unsigned short bn_u16x8;
-
-__device__ __forceinline__ float bnb2f(unsigned short u) {
-  bnbf16 v = *reinterpret_cast<bnbf16*>(&u);
-  return __bfloat162float(v);
+// statistics: (sum, sum of squares)
+__device__ __forceinline__ void bn_stat(float f, float (&acc)[2]) {
+  acc[0] += f;
+  acc[1] += f * f;
 }
 
-__device__ __forceinline__ void block_reduce2(float& a, float& b) {
-  a = wave_reduce_sum(a);
-  b = wave_reduce_sum(b);
-  __shared__ float red[2][4];
-  const int wid = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    red[0][wid] = a;
-    red[1][wid] = b;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
-      a += red[0][w];
-      b += red[1][w];
-    }
-  }
+// out = act(scale*y + shift (+ res))
+__device__ __forceinline__ float bn_apply(float y, float sc, float sh,
+                                          bool has_res, float res, int act) {
+  float f = y * sc + sh;
+  if (has_res) f += res;
+  return act_fwd(f, act);
 }
 
-__global__ void bn_stats_part_kernel(const bnbf16* __restrict__ y,
+// backward sums: (sum dy_eff, sum dy_eff*xhat), dy_eff = dy * act'(out)
+__device__ __forceinline__ void bn_bwd_stat(float dy, float y, float out,
+                                            float m, float rs, int act,
+                                            float (&acc)[2]) {
+  const float g = act_grad(dy, out, act);
+  acc[0] += g;
+  acc[1] += g * (y - m) * rs;
+}
+
+// dx; t1, t2 are the two backward sums over n
+__device__ __forceinline__ float bn_dx(float dy, float y, float out, float m,
+                                       float rs, float gm, float t1, float t2,
+                                       int act, int training) {
+  const float g = act_grad(dy, out, act);
+  if (!training) return gm * rs * g;
+  const float xh = (y - m) * rs;
+  return gm * rs * (g - t1 - xh * t2);
+}
+
+// the 16-byte run at p[i..i+7]
+__device__ __forceinline__ u16x8 bn_ld8(const bf16* p, long long i) {
+  return *reinterpret_cast<const u16x8*>(&p[i]);
+}
+
+__global__ void bn_stats_part_kernel(const bf16* __restrict__ y,
                                      float* __restrict__ psum,   // (S, C)
                                      float* __restrict__ psum2,  // (S, C)
                                      int C, long long HW, int B, int S) {
   const int c = blockIdx.y;
   const int sidx = blockIdx.x;
-  float s = 0.f, s2 = 0.f;
+  float acc[2] = {0.f, 0.f};
   for (int b = 0; b < B; ++b) {
-    const bnbf16* p = y + ((long long)b * C + c) * HW;
+    const bf16* p = y + ((long long)b * C + c) * HW;
     long long i0 = (long long)(sidx * (int)blockDim.x + threadIdx.x) * 8;
     long long stride = (long long)S * blockDim.x * 8;
     for (long long i = i0; i + 7 < HW; i += stride) {
-      const bn_u16x8 v = *reinterpret_cast<const bn_u16x8*>(&p[i]);
+      const u16x8 v = bn_ld8(p, i);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        float f = bnb2f(v[k]);
-        s += f;
-        s2 += f * f;
-      }
+      for (int k = 0; k < 8; ++k) bn_stat(b2f(v[k]), acc);
     }
-    if (sidx == 0 && threadIdx.x < (HW & 7)) {  // tail
-      float f = __bfloat162float(p[(HW & ~7LL) + threadIdx.x]);
-      s += f;
-      s2 += f * f;
-    }
+    if (sidx == 0 && threadIdx.x < (HW & 7))  // tail
+      bn_stat(b2f(p[(HW & ~7LL) + threadIdx.x]), acc);
   }
-  block_reduce2(s, s2);
+  const float* ws = block_wave_sums(acc);
   // per-slice plain stores into (S, C) partials: no atomics, and the
   // buffers need no zero-fill kernel (two fills per BN call was ~0.6 ms
   // per training step); bn_finalize sums the S slices.
   if (threadIdx.x == 0) {
-    psum[sidx * C + c] = s;
-    psum2[sidx * C + c] = s2;
+    psum[sidx * C + c] = sum4_serial(ws);
+    psum2[sidx * C + c] = sum4_serial(ws + BLOCK_WAVES);
   }
 }
 
@@ -84,9 +93,9 @@ __global__ void bn_stats_part_kernel(const bnbf16* __restrict__ y,
 // bn_finalize launch (one tiny kernel per BN call, ~0.6 ms/step across the
 // model) is gone. The first block of each channel also publishes
 // mean/rstd for the backward and advances the EMA running stats.
-__global__ void bn_apply_kernel(const bnbf16* __restrict__ y,
-                                const bnbf16* __restrict__ res,  // or null
-                                bnbf16* __restrict__ out,
+__global__ void bn_apply_kernel(const bf16* __restrict__ y,
+                                const bf16* __restrict__ res,  // or null
+                                bf16* __restrict__ out,
                                 const float* __restrict__ psum,  // (S,C)|null
                                 const float* __restrict__ psum2,
                                 const float* __restrict__ gamma,
@@ -126,46 +135,32 @@ __global__ void bn_apply_kernel(const bnbf16* __restrict__ y,
     }
   }
   const float sc = gamma[c] * rs, sh = beta[c] - m * sc;
-  const bnbf16* p = y + (long long)bc * HW;
-  const bnbf16* q = res ? res + (long long)bc * HW : nullptr;
-  bnbf16* o = out + (long long)bc * HW;
+  const bf16* p = y + (long long)bc * HW;
+  const bf16* q = res ? res + (long long)bc * HW : nullptr;
+  bf16* o = out + (long long)bc * HW;
   long long i0 = (long long)(blockIdx.x * blockDim.x + threadIdx.x) * 8;
   long long stride = (long long)gridDim.x * blockDim.x * 8;
   for (long long i = i0; i + 7 < HW; i += stride) {
-    const bn_u16x8 v = *reinterpret_cast<const bn_u16x8*>(&p[i]);
-    bn_u16x8 rv;
-    if (q) rv = *reinterpret_cast<const bn_u16x8*>(&q[i]);
-    bn_u16x8 r;
+    const u16x8 v = bn_ld8(p, i);
+    u16x8 rv;
+    if (q) rv = bn_ld8(q, i);
+    u16x8 r;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      float f = bnb2f(v[k]) * sc + sh;
-      if (q) f += bnb2f(rv[k]);
-      if (act == 1) f = fmaxf(f, 0.f);
-      else if (act == 2) f = fmaxf(f, 0.2f * f);
-      bnbf16 h = __float2bfloat16(f);
-      r[k] = *reinterpret_cast<unsigned short*>(&h);
-    }
-    *reinterpret_cast<bn_u16x8*>(&o[i]) = r;
+    for (int k = 0; k < 8; ++k)
+      r[k] = f2bits(
+          bn_apply(b2f(v[k]), sc, sh, q != nullptr, q ? b2f(rv[k]) : 0.f, act));
+    *reinterpret_cast<u16x8*>(&o[i]) = r;
   }
   if (blockIdx.x == 0 && threadIdx.x < (HW & 7)) {
     long long j = (HW & ~7LL) + threadIdx.x;
-    float f = __bfloat162float(p[j]) * sc + sh;
-    if (q) f += __bfloat162float(q[j]);
-    if (act == 1) f = fmaxf(f, 0.f);
-    else if (act == 2) f = fmaxf(f, 0.2f * f);
-    o[j] = __float2bfloat16(f);
+    o[j] = f2b(
+        bn_apply(b2f(p[j]), sc, sh, q != nullptr, q ? b2f(q[j]) : 0.f, act));
   }
 }
 
-__device__ __forceinline__ float bn_actp(float g, float ov, int act) {
-  if (act == 1) return ov > 0.f ? g : 0.f;
-  if (act == 2) return ov > 0.f ? g : 0.2f * g;
-  return g;
-}
-
-__global__ void bn_bwd_part_kernel(const bnbf16* __restrict__ dy,
-                                   const bnbf16* __restrict__ y,
-                                   const bnbf16* __restrict__ out,
+__global__ void bn_bwd_part_kernel(const bf16* __restrict__ dy,
+                                   const bf16* __restrict__ y,
+                                   const bf16* __restrict__ out,
                                    const float* __restrict__ mean,
                                    const float* __restrict__ rstd,
                                    float* __restrict__ s1,
@@ -175,43 +170,38 @@ __global__ void bn_bwd_part_kernel(const bnbf16* __restrict__ dy,
   const int c = blockIdx.y;
   const int sidx = blockIdx.x;
   const float m = mean[c], rs = rstd[c];
-  float a = 0.f, b2 = 0.f;
+  float acc[2] = {0.f, 0.f};
   for (int b = 0; b < B; ++b) {
     const long long base = ((long long)b * C + c) * HW;
     long long i0 = (long long)(sidx * (int)blockDim.x + threadIdx.x) * 8;
     long long stride = (long long)S * blockDim.x * 8;
     for (long long i = i0; i + 7 < HW; i += stride) {
-      const bn_u16x8 gv = *reinterpret_cast<const bn_u16x8*>(&dy[base + i]);
-      const bn_u16x8 yv = *reinterpret_cast<const bn_u16x8*>(&y[base + i]);
-      const bn_u16x8 ov = *reinterpret_cast<const bn_u16x8*>(&out[base + i]);
+      const u16x8 gv = bn_ld8(dy, base + i);
+      const u16x8 yv = bn_ld8(y, base + i);
+      const u16x8 ov = bn_ld8(out, base + i);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        float g = bn_actp(bnb2f(gv[k]), bnb2f(ov[k]), act);
-        a += g;
-        b2 += g * (bnb2f(yv[k]) - m) * rs;
-      }
+      for (int k = 0; k < 8; ++k)
+        bn_bwd_stat(b2f(gv[k]), b2f(yv[k]), b2f(ov[k]), m, rs, act, acc);
     }
     if (sidx == 0 && threadIdx.x < (HW & 7)) {
       long long j = base + (HW & ~7LL) + threadIdx.x;
-      float g = bn_actp(__bfloat162float(dy[j]), __bfloat162float(out[j]), act);
-      a += g;
-      b2 += g * (__bfloat162float(y[j]) - m) * rs;
+      bn_bwd_stat(b2f(dy[j]), b2f(y[j]), b2f(out[j]), m, rs, act, acc);
     }
   }
-  block_reduce2(a, b2);
+  const float* ws = block_wave_sums(acc);
   // plain per-slice stores (deterministic: the host reduces the (S, C)
   // partials with one ordered at::sum — fp32 atomicAdd order varies
   // between runs and was the one nondeterminism in the BN backward)
   if (threadIdx.x == 0) {
-    s1[(long long)sidx * C + c] = a;
-    s2[(long long)sidx * C + c] = b2;
+    s1[(long long)sidx * C + c] = sum4_serial(ws);
+    s2[(long long)sidx * C + c] = sum4_serial(ws + BLOCK_WAVES);
   }
 }
 
-__global__ void bn_bwd_apply_kernel(const bnbf16* __restrict__ dy,
-                                    const bnbf16* __restrict__ y,
-                                    const bnbf16* __restrict__ out,
-                                    bnbf16* __restrict__ dx,
+__global__ void bn_bwd_apply_kernel(const bf16* __restrict__ dy,
+                                    const bf16* __restrict__ y,
+                                    const bf16* __restrict__ out,
+                                    bf16* __restrict__ dx,
                                     const float* __restrict__ mean,
                                     const float* __restrict__ rstd,
                                     const float* __restrict__ gamma,
@@ -227,36 +217,20 @@ __global__ void bn_bwd_apply_kernel(const bnbf16* __restrict__ dy,
   long long i0 = (long long)(blockIdx.x * blockDim.x + threadIdx.x) * 8;
   long long stride = (long long)gridDim.x * blockDim.x * 8;
   for (long long i = i0; i + 7 < HW; i += stride) {
-    const bn_u16x8 gv = *reinterpret_cast<const bn_u16x8*>(&dy[base + i]);
-    const bn_u16x8 ov = *reinterpret_cast<const bn_u16x8*>(&out[base + i]);
-    const bn_u16x8 yv = *reinterpret_cast<const bn_u16x8*>(&y[base + i]);
-    bn_u16x8 r;
+    const u16x8 gv = bn_ld8(dy, base + i);
+    const u16x8 ov = bn_ld8(out, base + i);
+    const u16x8 yv = bn_ld8(y, base + i);
+    u16x8 r;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      float g = bn_actp(bnb2f(gv[k]), bnb2f(ov[k]), act);
-      float v;
-      if (training) {
-        const float xh = (bnb2f(yv[k]) - m) * rs;
-        v = gm * rs * (g - t1 - xh * t2);
-      } else {
-        v = gm * rs * g;
-      }
-      bnbf16 h = __float2bfloat16(v);
-      r[k] = *reinterpret_cast<unsigned short*>(&h);
-    }
-    *reinterpret_cast<bn_u16x8*>(&dx[base + i]) = r;
+    for (int k = 0; k < 8; ++k)
+      r[k] = f2bits(bn_dx(b2f(gv[k]), b2f(yv[k]), b2f(ov[k]), m, rs, gm, t1,
+                          t2, act, training));
+    *reinterpret_cast<u16x8*>(&dx[base + i]) = r;
   }
   if (blockIdx.x == 0 && threadIdx.x < (HW & 7)) {
     long long j = base + (HW & ~7LL) + threadIdx.x;
-    float g = bn_actp(__bfloat162float(dy[j]), __bfloat162float(out[j]), act);
-    float v;
-    if (training) {
-      const float xh = (__bfloat162float(y[j]) - m) * rs;
-      v = gm * rs * (g - t1 - xh * t2);
-    } else {
-      v = gm * rs * g;
-    }
-    dx[j] = __float2bfloat16(v);
+    dx[j] = f2b(bn_dx(b2f(dy[j]), b2f(y[j]), b2f(out[j]), m, rs, gm, t1, t2,
+                      act, training));
   }
 }
 
@@ -271,10 +245,17 @@ std::vector<torch::Tensor> bn_fwd(torch::Tensor y, torch::Tensor gamma,
                                   torch::Tensor rvar, double momentum,
                                   double eps, bool training, int64_t act,
                                   c10::optional<torch::Tensor> residual) {
-  CHECK_CUDA_CONTIG(y);
-  TORCH_CHECK(y.scalar_type() == torch::kBFloat16, "bn: y must be bf16");
+  check_arg(y, "bn_fwd: y", torch::kBFloat16);
+  TORCH_CHECK(y.dim() == 4, "bn_fwd: y must be NCHW");
   const int B = (int)y.size(0), C = (int)y.size(1);
   const long long HW = (long long)y.size(2) * y.size(3);
+  check_arg_numel(gamma, "bn_fwd: gamma", torch::kFloat32, C);
+  check_arg_numel(beta, "bn_fwd: beta", torch::kFloat32, C);
+  check_arg_numel(rmean, "bn_fwd: rmean", torch::kFloat32, C);
+  check_arg_numel(rvar, "bn_fwd: rvar", torch::kFloat32, C);
+  if (residual.has_value())
+    check_arg_shape(*residual, "bn_fwd: residual", torch::kBFloat16,
+                    y.sizes());
   auto optsF = y.options().dtype(torch::kFloat32);
   auto mean = torch::empty({C}, optsF);
   auto rstd = torch::empty({C}, optsF);
@@ -287,19 +268,16 @@ std::vector<torch::Tensor> bn_fwd(torch::Tensor y, torch::Tensor gamma,
     parts = torch::empty({2, S, C}, optsF);  // written fully: no fill
     psum = parts.data_ptr<float>();
     psum2 = psum + (long long)S * C;
-    hipLaunchKernelGGL(bn_stats_part_kernel, dim3(S, C), dim3(256), 0, stream,
-                       (const bnbf16*)y.data_ptr(), psum, psum2, C, HW, B, S);
+    hipLaunchKernelGGL(bn_stats_part_kernel, dim3(S, C), dim3(BLOCK_THREADS),
+                       0, stream, ptr<const bf16>(y), psum, psum2, C, HW, B,
+                       S);
   }
   auto out = torch::empty_like(y);
-  const bnbf16* resp = nullptr;
-  if (residual.has_value()) {
-    CHECK_CUDA_CONTIG(residual.value());
-    resp = (const bnbf16*)residual->data_ptr();
-  }
-  hipLaunchKernelGGL(bn_apply_kernel,
-                     dim3(S, B * C), dim3(256), 0, stream,
-                     (const bnbf16*)y.data_ptr(), resp, (bnbf16*)out.data_ptr(),
-                     psum, psum2, gamma.data_ptr<float>(),
+  hipLaunchKernelGGL(bn_apply_kernel, dim3(S, B * C), dim3(BLOCK_THREADS), 0,
+                     stream, ptr<const bf16>(y),
+                     residual.has_value() ? ptr<const bf16>(*residual)
+                                          : nullptr,
+                     ptr<bf16>(out), psum, psum2, gamma.data_ptr<float>(),
                      beta.data_ptr<float>(), mean.data_ptr<float>(),
                      rstd.data_ptr<float>(), rmean.data_ptr<float>(),
                      rvar.data_ptr<float>(), C, HW, S,
@@ -312,18 +290,23 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor dy, torch::Tensor y,
                                   torch::Tensor out, torch::Tensor mean,
                                   torch::Tensor rstd, torch::Tensor gamma,
                                   bool training, int64_t act) {
-  CHECK_CUDA_CONTIG(dy);
-  CHECK_CUDA_CONTIG(y);
+  check_arg(y, "bn_bwd: y", torch::kBFloat16);
+  TORCH_CHECK(y.dim() == 4, "bn_bwd: y must be NCHW");
   const int B = (int)y.size(0), C = (int)y.size(1);
   const long long HW = (long long)y.size(2) * y.size(3);
+  check_arg_shape(dy, "bn_bwd: dy", torch::kBFloat16, y.sizes());
+  check_arg_shape(out, "bn_bwd: out", torch::kBFloat16, y.sizes());
+  check_arg_numel(mean, "bn_bwd: mean", torch::kFloat32, C);
+  check_arg_numel(rstd, "bn_bwd: rstd", torch::kFloat32, C);
+  check_arg_numel(gamma, "bn_bwd: gamma", torch::kFloat32, C);
   auto optsF = y.options().dtype(torch::kFloat32);
   auto stream = at::cuda::getCurrentCUDAStream();
   const int S = _spatial_chunks(HW);
   // (2, S, C) plain-store partials -> one ordered sum (deterministic)
   auto parts = torch::empty({2, S, C}, optsF);
-  hipLaunchKernelGGL(bn_bwd_part_kernel, dim3(S, C), dim3(256), 0, stream,
-                     (const bnbf16*)dy.data_ptr(), (const bnbf16*)y.data_ptr(),
-                     (const bnbf16*)out.data_ptr(), mean.data_ptr<float>(),
+  hipLaunchKernelGGL(bn_bwd_part_kernel, dim3(S, C), dim3(BLOCK_THREADS), 0,
+                     stream, ptr<const bf16>(dy), ptr<const bf16>(y),
+                     ptr<const bf16>(out), mean.data_ptr<float>(),
                      rstd.data_ptr<float>(), parts[0].data_ptr<float>(),
                      parts[1].data_ptr<float>(), C, HW, B, S, (int)act);
   auto sbuf = parts.sum(1);  // (2, C), contiguous
@@ -331,12 +314,12 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor dy, torch::Tensor y,
   auto s2 = sbuf[1];
   auto dx = torch::empty_like(y);
   hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(_spatial_chunks(HW), B * C),
-                     dim3(256), 0, stream, (const bnbf16*)dy.data_ptr(),
-                     (const bnbf16*)y.data_ptr(), (const bnbf16*)out.data_ptr(),
-                     (bnbf16*)dx.data_ptr(), mean.data_ptr<float>(),
-                     rstd.data_ptr<float>(), gamma.data_ptr<float>(),
-                     s1.data_ptr<float>(), s2.data_ptr<float>(), C, HW,
-                     1.f / (float)(B * HW), (int)act, training ? 1 : 0);
+                     dim3(BLOCK_THREADS), 0, stream, ptr<const bf16>(dy),
+                     ptr<const bf16>(y), ptr<const bf16>(out), ptr<bf16>(dx),
+                     mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                     gamma.data_ptr<float>(), s1.data_ptr<float>(),
+                     s2.data_ptr<float>(), C, HW, 1.f / (float)(B * HW),
+                     (int)act, training ? 1 : 0);
   // dgamma = s2, dbeta = s1
   return {dx, s2, s1};
 }

@@ -295,20 +295,14 @@ torch::Tensor panel_gather(torch::Tensor src, torch::Tensor ktab) {
   const int64_t KPA = ((Kl + 63) & ~63) + CONV_AP;
   auto out = torch::empty({rows, KPA}, src.options().dtype(torch::kBFloat16));
   const long long total = rows * KPA;
-  const int grid = (int)std::min<long long>((total + 255) / 256, 4096);
   auto stream = at::cuda::getCurrentCUDAStream();
-  if (src.scalar_type() == torch::kFloat32) {
-    hipLaunchKernelGGL((panel_gather_kernel<float>), dim3(grid), dim3(256), 0,
-                       stream, src.data_ptr<float>(), ktab.data_ptr<int>(),
-                       (cvbf16*)out.data_ptr(), (int)rows, (int)Kl, (int)KPA,
-                       (int)src.size(1));
-  } else {
-    TORCH_CHECK(src.scalar_type() == torch::kBFloat16, "panel src dtype");
-    hipLaunchKernelGGL((panel_gather_kernel<cvbf16>), dim3(grid), dim3(256),
-                       0, stream, (const cvbf16*)src.data_ptr(),
-                       ktab.data_ptr<int>(), (cvbf16*)out.data_ptr(),
-                       (int)rows, (int)Kl, (int)KPA, (int)src.size(1));
-  }
+  dispatch_f32_bf16(src, "panel_gather: src", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((panel_gather_kernel<T>), dim3(ew_grid(total)),
+                       dim3(256), 0, stream, ptr<const T>(src),
+                       ktab.data_ptr<int>(), ptr<cvbf16>(out), (int)rows,
+                       (int)Kl, (int)KPA, (int)src.size(1));
+  });
   return out;
 }
 
@@ -318,19 +312,12 @@ torch::Tensor act_bwd(torch::Tensor dy, torch::Tensor y, int64_t act) {
   const long long n = dy.numel();
   auto out = torch::empty_like(y);  // y is bf16, same shape
   auto stream = at::cuda::getCurrentCUDAStream();
-  const int grid = (int)std::min<long long>((n + 255) / 256, 4096);
-  if (dy.scalar_type() == torch::kFloat32) {
-    hipLaunchKernelGGL((act_bwd_kernel<float>), dim3(grid), dim3(256), 0,
-                       stream, dy.data_ptr<float>(),
-                       (const cvbf16*)y.data_ptr(), (cvbf16*)out.data_ptr(), n,
-                       (int)act);
-  } else {
-    TORCH_CHECK(dy.scalar_type() == torch::kBFloat16, "act_bwd: fp32/bf16");
-    hipLaunchKernelGGL((act_bwd_kernel<cvbf16>), dim3(grid), dim3(256), 0,
-                       stream, (const cvbf16*)dy.data_ptr(),
-                       (const cvbf16*)y.data_ptr(), (cvbf16*)out.data_ptr(), n,
-                       (int)act);
-  }
+  dispatch_f32_bf16(dy, "act_bwd: dy", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((act_bwd_kernel<T>), dim3(ew_grid(n)), dim3(256), 0,
+                       stream, ptr<const T>(dy), ptr<const cvbf16>(y),
+                       ptr<cvbf16>(out), n, (int)act);
+  });
   return out;
 }
 
@@ -349,20 +336,14 @@ torch::Tensor wmat_make(torch::Tensor w1, int64_t khw, int64_t mode) {
   auto out = torch::empty({rows, KPA},
                           w1.options().dtype(torch::kBFloat16));
   const long long total = rows * KPA;
-  const int grid = (int)std::min<long long>((total + 255) / 256, 4096);
   auto stream = at::cuda::getCurrentCUDAStream();
-  if (w1.scalar_type() == torch::kFloat32) {
-    hipLaunchKernelGGL((wmat_make_kernel<float>), dim3(grid), dim3(256), 0,
-                       stream, w1.data_ptr<float>(), (cvbf16*)out.data_ptr(),
+  dispatch_f32_bf16(w1, "wmat_make: w1", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((wmat_make_kernel<T>), dim3(ew_grid(total)), dim3(256),
+                       0, stream, ptr<const T>(w1), ptr<cvbf16>(out),
                        (int)rows, (int)kout, (int)K, (int)khw, (int)KPA,
                        (int)mode, (int)nrows);
-  } else {
-    TORCH_CHECK(w1.scalar_type() == torch::kBFloat16, "wmat_make: fp32/bf16");
-    hipLaunchKernelGGL((wmat_make_kernel<cvbf16>), dim3(grid), dim3(256), 0,
-                       stream, (const cvbf16*)w1.data_ptr(),
-                       (cvbf16*)out.data_ptr(), (int)rows, (int)kout, (int)K,
-                       (int)khw, (int)KPA, (int)mode, (int)nrows);
-  }
+  });
   return out;
 }
 

@@ -14,8 +14,7 @@
 // reduced-precision path, not the default). Output stays bf16.
 
 #pragma once
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
+#include "device_common.h"
 #include <hip/hip_fp8.h>
 
 namespace dsin {
@@ -174,10 +173,7 @@ void conv_fwd_fp8_kernel(const f8* __restrict__ xpad,   // (Ci, Hp, Wp) e4m3
       for (int reg = 0; reg < 4; ++reg) {
         const int m = m0 + mi * 16 + kgrp * 4 + reg;
         if (m < M) {
-          float v = acc[mi][reg] + bv;
-          if (act == 1) v = fmaxf(v, 0.f);
-          else if (act == 2) v = fmaxf(v, 0.2f * v);
-          o[m] = __float2bfloat16(v);
+          o[m] = __float2bfloat16(act_fwd(acc[mi][reg] + bv, act));
         }
       }
     }

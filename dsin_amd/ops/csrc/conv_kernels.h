@@ -30,8 +30,7 @@
 // the slices with one sum(0).
 
 #pragma once
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
+#include "device_common.h"
 
 namespace dsin {
 
@@ -114,10 +113,7 @@ __device__ __forceinline__ unsigned short cv_load_or_zero(const cvbf16* x,
 // Epilogue value of the three forward kernels: bias, then act (0 none,
 // 1 ReLU, 2 leaky 0.2).
 __device__ __forceinline__ float cv_bias_act(float v, float bv, int act) {
-  v += bv;
-  if (act == 1) v = fmaxf(v, 0.f);
-  else if (act == 2) v = fmaxf(v, 0.2f * v);
-  return v;
+  return act_fwd(v + bv, act);
 }
 
 // Stage one 8-element run from the virtual image pad(stuff(x, SV)) at
@@ -1028,11 +1024,7 @@ __global__ void act_bwd_kernel(const T* __restrict__ dy,
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long stride = (long long)gridDim.x * blockDim.x;
   for (; i < n; i += stride) {
-    float g = (float)dy[i];
-    float yy = cvb2f(y[i]);
-    if (act == 1) g = yy > 0.f ? g : 0.f;
-    else if (act == 2) g = yy > 0.f ? g : 0.2f * g;
-    out[i] = cvf2b(g);
+    out[i] = cvf2b(act_grad((float)dy[i], cvb2f(y[i]), act));
   }
 }
 

@@ -58,18 +58,15 @@ constexpr int MS_B_Y = 5 * MS_BI * MS_BD;               // 10920
 static_assert(3 * MS_BD * MS_BD <= MS_B_X, "derivative maps must fit in X");
 static_assert(3 * MS_TILE * MS_BD <= MS_B_Y, "vertical pass must fit in Y");
 
-__device__ __forceinline__ float ms_ld(const float* p, long long i) {
-  return p[i];
-}
-__device__ __forceinline__ float ms_ld(const bf16* p, long long i) {
-  return b2f(p[i]);
-}
-__device__ __forceinline__ void ms_st(float* p, long long i, float v) {
-  p[i] = v;
-}
-__device__ __forceinline__ void ms_st(bf16* p, long long i, float v) {
-  p[i] = f2b(v);
-}
+// Forward and backward each carry the five-map row pass, the column pass and
+// the ssim / cs terms (s11 ... lum), and forward its own block sum, written
+// out. They stay so on purpose: hipcc contracts these expressions per
+// kernel (forward takes u1*u1 + u2*u2 + c1 as a packed multiply and add,
+// backward as an fma; e11 - m1*m1 is an fma in both), and moving any of the
+// pieces into a shared function (tried: row pass, column pass, terms, and
+// device_common.h's block_wave_sums for the tail) made forward contract
+// differently and changed the last bit of its ssim sums
+// (profiles/r14_pointwise_device.md).
 
 __device__ __forceinline__ int ms_clamp(int v, int lo, int hi) {
   return min(max(v, lo), hi);
@@ -107,8 +104,8 @@ __global__ __launch_bounds__(MS_THREADS) void ssim_scale_fwd_kernel(
     const int r = i / hw, c = i - r * hw;
     const int gy = min(y0 + r, H - 1), gx = min(x0 + c, W - 1);
     const long long o = plane + (long long)gy * W + gx;
-    sA[i] = ms_ld(a, o) - MS_SHIFT;
-    sB[i] = ms_ld(b, o) - MS_SHIFT;
+    sA[i] = ld_f32(a, o) - MS_SHIFT;
+    sB[i] = ld_f32(b, o) - MS_SHIFT;
   }
   __syncthreads();
 
@@ -224,8 +221,8 @@ __global__ __launch_bounds__(MS_THREADS) void ssim_scale_bwd_kernel(
     const int gy = ms_clamp(oy0 + r, 0, H - 1);
     const int gx = ms_clamp(ox0 + c, 0, W - 1);
     const long long o = plane + (long long)gy * W + gx;
-    sA[i] = ms_ld(a, o) - MS_SHIFT;
-    sB[i] = ms_ld(b, o) - MS_SHIFT;
+    sA[i] = ld_f32(a, o) - MS_SHIFT;
+    sB[i] = ld_f32(b, o) - MS_SHIFT;
   }
   __syncthreads();
 
@@ -323,10 +320,10 @@ __global__ __launch_bounds__(MS_THREADS) void ssim_scale_bwd_kernel(
     const int y = y0 + r, x = x0 + c;
     const long long o =
         plane + (long long)min(y, H - 1) * W + min(x, W - 1);
-    const float av = ms_ld(a, o) - MS_SHIFT;
-    const float bv = ms_ld(b, o) - MS_SHIFT;
+    const float av = ld_f32(a, o) - MS_SHIFT;
+    const float bv = ld_f32(b, o) - MS_SHIFT;
     const float g = gm + 2.f * bv * gv + av * g12;
-    if (y < H && x < W) ms_st(gb, o, g);
+    if (y < H && x < W) st_f32(gb, o, g);
   }
 }
 
@@ -349,10 +346,10 @@ __global__ void down2_fwd_kernel(const T* __restrict__ x,
     const int xb = (xa + 1 < W) ? xa + 1 : W - 2;
     const int yb = (ya + 1 < H) ? ya + 1 : H - 2;
     const long long base = p * H * W;
-    const float h0 = 0.5f * ms_ld(x, base + (long long)ya * W + xa) +
-                     0.5f * ms_ld(x, base + (long long)ya * W + xb);
-    const float h1 = 0.5f * ms_ld(x, base + (long long)yb * W + xa) +
-                     0.5f * ms_ld(x, base + (long long)yb * W + xb);
+    const float h0 = 0.5f * ld_f32(x, base + (long long)ya * W + xa) +
+                     0.5f * ld_f32(x, base + (long long)ya * W + xb);
+    const float h1 = 0.5f * ld_f32(x, base + (long long)yb * W + xa) +
+                     0.5f * ld_f32(x, base + (long long)yb * W + xb);
     out[i] = 0.5f * h0 + 0.5f * h1;
   }
 }
@@ -381,7 +378,7 @@ __global__ void down2_bwd_kernel(const float* __restrict__ g,
     const float gbb = gp[(long long)oyb * Wo + oxb];
     const float top = gaa + (ex ? gab : 0.f);
     const float bot = gba + (ex ? gbb : 0.f);
-    ms_st(gx, i, 0.25f * (top + (ey ? bot : 0.f)));
+    st_f32(gx, i, 0.25f * (top + (ey ? bot : 0.f)));
   }
 }
 
@@ -435,19 +432,17 @@ torch::Tensor ssim_scale_fwd(torch::Tensor a, torch::Tensor b,
   auto parts =
       torch::empty({2, g.nblk}, a.options().dtype(torch::kFloat32));
   auto stream = at::cuda::getCurrentCUDAStream();
-  const bool af = a.scalar_type() == torch::kFloat32;
-  const bool bf = b.scalar_type() == torch::kFloat32;
-#define MSF(TA, TB)                                                          \
-  hipLaunchKernelGGL((ssim_scale_fwd_kernel<TA, TB>), dim3(g.nblk),          \
-                     dim3(MS_THREADS), 0, stream, (const TA*)a.data_ptr(),   \
-                     (const TB*)b.data_ptr(), taps.data_ptr<float>(),        \
-                     parts.data_ptr<float>(), g.H, g.W, g.T, g.tiles_x,      \
-                     g.tiles_y, g.nblk, (float)c1, (float)c2)
-  if (af && bf) MSF(float, float);
-  else if (af && !bf) MSF(float, bf16);
-  else if (!af && bf) MSF(bf16, float);
-  else MSF(bf16, bf16);
-#undef MSF
+  dispatch_f32_bf16(a, "ssim_scale_fwd: a", [&](auto ta) {
+    dispatch_f32_bf16(b, "ssim_scale_fwd: b", [&](auto tb) {
+      using TA = decltype(ta);
+      using TB = decltype(tb);
+      hipLaunchKernelGGL((ssim_scale_fwd_kernel<TA, TB>), dim3(g.nblk),
+                         dim3(MS_THREADS), 0, stream, ptr<const TA>(a),
+                         ptr<const TB>(b), taps.data_ptr<float>(),
+                         parts.data_ptr<float>(), g.H, g.W, g.T, g.tiles_x,
+                         g.tiles_y, g.nblk, (float)c1, (float)c2);
+    });
+  });
   return parts;
 }
 
@@ -456,43 +451,38 @@ std::vector<torch::Tensor> ssim_scale_bwd(
     c10::optional<torch::Tensor> g_ssim, c10::optional<torch::Tensor> g_cs,
     double c1, double c2, bool need_ga, bool need_gb) {
   const MsGeom g = ms_geom(a, b, taps, true);
-  auto scalar = [](const c10::optional<torch::Tensor>& t) -> const float* {
+  auto scalar = [](const c10::optional<torch::Tensor>& t,
+                   const char* what) -> const float* {
     if (!t.has_value()) return nullptr;
-    TORCH_CHECK(t->is_cuda() && t->numel() == 1 &&
-                    t->scalar_type() == torch::kFloat32,
-                "ssim_scale_bwd: upstream grads must be fp32 GPU scalars");
+    check_arg_numel(*t, what, torch::kFloat32, 1);
     return t->data_ptr<float>();
   };
-  const float* gs = scalar(g_ssim);
-  const float* gc = scalar(g_cs);
+  const float* gs = scalar(g_ssim, "ssim_scale_bwd: g_ssim");
+  const float* gc = scalar(g_cs, "ssim_scale_bwd: g_cs");
   const float inv_n = (float)(1.0 / ((double)g.P * (g.H - g.T + 1) *
                                      (g.W - g.T + 1)));
   auto ga = need_ga ? torch::empty_like(a) : torch::Tensor();
   auto gb = need_gb ? torch::empty_like(b) : torch::Tensor();
   auto stream = at::cuda::getCurrentCUDAStream();
-  const bool af = a.scalar_type() == torch::kFloat32;
-  const bool bf = b.scalar_type() == torch::kFloat32;
   // (other, target): the kernel differentiates w.r.t. its second image
-#define MSB(TO, TT, other, target, out)                                      \
-  hipLaunchKernelGGL((ssim_scale_bwd_kernel<TO, TT>), dim3(g.nblk),          \
-                     dim3(MS_THREADS), 0, stream,                            \
-                     (const TO*)other.data_ptr(),                            \
-                     (const TT*)target.data_ptr(), taps.data_ptr<float>(),   \
-                     gs, gc, (TT*)out.data_ptr(), g.H, g.W, g.T, g.tiles_x,  \
-                     g.tiles_y, inv_n, (float)c1, (float)c2)
-  if (need_gb) {
-    if (af && bf) MSB(float, float, a, b, gb);
-    else if (af && !bf) MSB(float, bf16, a, b, gb);
-    else if (!af && bf) MSB(bf16, float, a, b, gb);
-    else MSB(bf16, bf16, a, b, gb);
-  }
-  if (need_ga) {
-    if (af && bf) MSB(float, float, b, a, ga);
-    else if (af && !bf) MSB(bf16, float, b, a, ga);
-    else if (!af && bf) MSB(float, bf16, b, a, ga);
-    else MSB(bf16, bf16, b, a, ga);
-  }
-#undef MSB
+  auto launch = [&](const torch::Tensor& other, const torch::Tensor& target,
+                    torch::Tensor& out) {
+    dispatch_f32_bf16(other, "ssim_scale_bwd: image", [&](auto to) {
+      dispatch_f32_bf16(target, "ssim_scale_bwd: image", [&](auto tt) {
+        using TO = decltype(to);
+        using TT = decltype(tt);
+        hipLaunchKernelGGL((ssim_scale_bwd_kernel<TO, TT>), dim3(g.nblk),
+                           dim3(MS_THREADS), 0, stream, ptr<const TO>(other),
+                           ptr<const TT>(target), taps.data_ptr<float>(), gs,
+                           gc, ptr<TT>(out), g.H, g.W, g.T, g.tiles_x,
+                           g.tiles_y, inv_n, (float)c1, (float)c2);
+      });
+    });
+  };
+  if (need_gb) launch(a, b, gb);
+  // the gradient w.r.t. a swaps the images, and with them the kernel's two
+  // element types: the dispatch follows the tensors in the order given here
+  if (need_ga) launch(b, a, ga);
   return {ga, gb};
 }
 
@@ -507,19 +497,13 @@ torch::Tensor down2_fwd(torch::Tensor x) {
                           x.options().dtype(torch::kFloat32));
   const long long total = out.numel();
   if (total == 0) return out;
-  const int grid = (int)std::min<long long>((total + 255) / 256, 4096);
   auto stream = at::cuda::getCurrentCUDAStream();
-  if (x.scalar_type() == torch::kFloat32) {
-    hipLaunchKernelGGL((down2_fwd_kernel<float>), dim3(grid), dim3(256), 0,
-                       stream, x.data_ptr<float>(), out.data_ptr<float>(), H,
-                       W, Ho, Wo, total);
-  } else {
-    TORCH_CHECK(x.scalar_type() == torch::kBFloat16,
-                "downsample2: fp32 or bf16");
-    hipLaunchKernelGGL((down2_fwd_kernel<bf16>), dim3(grid), dim3(256), 0,
-                       stream, (const bf16*)x.data_ptr(),
+  dispatch_f32_bf16(x, "downsample2: x", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((down2_fwd_kernel<T>), dim3(ew_grid(total)),
+                       dim3(BLOCK_THREADS), 0, stream, ptr<const T>(x),
                        out.data_ptr<float>(), H, W, Ho, Wo, total);
-  }
+  });
   return out;
 }
 
@@ -538,17 +522,13 @@ torch::Tensor down2_bwd(torch::Tensor g, int64_t H64, int64_t W64,
       g.options().dtype(bf16_out ? torch::kBFloat16 : torch::kFloat32));
   const long long total = gx.numel();
   if (total == 0) return gx;
-  const int grid = (int)std::min<long long>((total + 255) / 256, 4096);
   auto stream = at::cuda::getCurrentCUDAStream();
-  if (bf16_out) {
-    hipLaunchKernelGGL((down2_bwd_kernel<bf16>), dim3(grid), dim3(256), 0,
-                       stream, g.data_ptr<float>(), (bf16*)gx.data_ptr(), H,
-                       W, Ho, Wo, total);
-  } else {
-    hipLaunchKernelGGL((down2_bwd_kernel<float>), dim3(grid), dim3(256), 0,
-                       stream, g.data_ptr<float>(), gx.data_ptr<float>(), H,
-                       W, Ho, Wo, total);
-  }
+  dispatch_f32_bf16(gx, "downsample2 backward: gx", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((down2_bwd_kernel<T>), dim3(ew_grid(total)),
+                       dim3(BLOCK_THREADS), 0, stream, g.data_ptr<float>(),
+                       ptr<T>(gx), H, W, Ho, Wo, total);
+  });
   return gx;
 }
 

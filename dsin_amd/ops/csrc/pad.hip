@@ -23,21 +23,14 @@ torch::Tensor pad_stuff_e4m3(torch::Tensor x, int64_t pt, int64_t pb,
                             x.options().dtype(torch::kByte));
   auto out = store.narrow(0, 0, B * n_img).view({B, C, Hp, Wp});
   long long total = (long long)B * n_img;
-  int grid = (int)std::min<long long>((total + 255) / 256, 8192);
   auto stream = at::cuda::getCurrentCUDAStream();
-  if (x.scalar_type() == torch::kFloat32) {
-    hipLaunchKernelGGL((pad_stuff_fp8_kernel<float>), dim3(grid), dim3(256),
-                       0, stream, x.data_ptr<float>(), (f8*)out.data_ptr(),
-                       C, H, W, Hp, Wp, (int)pt, (int)pl, (int)stride, n_img,
+  dispatch_f32_bf16(x, "pad_stuff_e4m3: x", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((pad_stuff_fp8_kernel<T>), dim3(ew_grid(total, 8192)),
+                       dim3(256), 0, stream, ptr<const T>(x), ptr<f8>(out), C,
+                       H, W, Hp, Wp, (int)pt, (int)pl, (int)stride, n_img,
                        (long long)C * H * W, B);
-  } else if (x.scalar_type() == torch::kBFloat16) {
-    hipLaunchKernelGGL((pad_stuff_fp8_kernel<bf16>), dim3(grid), dim3(256),
-                       0, stream, (const bf16*)x.data_ptr(),
-                       (f8*)out.data_ptr(), C, H, W, Hp, Wp, (int)pt,
-                       (int)pl, (int)stride, n_img, (long long)C * H * W, B);
-  } else {
-    TORCH_CHECK(false, "pad_stuff_e4m3: fp32 or bf16 input only");
-  }
+  });
   return out;
 }
 

@@ -108,34 +108,24 @@ __global__ void quantize_bwd_kernel(const float* __restrict__ g,
   // host reduces the (grid, L) partials with one ordered sum. (fp32
   // atomicAdd — across blocks or across the 4 waves of a block — has a
   // run-varying order and was one of the two nondeterminism sources.)
-  __shared__ float red[4][MAX_L];
-  const int wv = threadIdx.x >> 6;
-#pragma unroll 8
-  for (int l = 0; l < L; ++l) {
-    float v = wave_reduce_sum(gcl[l]);
-    if ((threadIdx.x & 63) == 0) red[wv][l] = v;
-  }
-  __syncthreads();
+  const float* ws = block_wave_sums(gcl, L);
   if (threadIdx.x < L)
     gc[(int64_t)blockIdx.x * L + threadIdx.x] =
-        red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] +
-        red[3][threadIdx.x];
+        sum4_serial(ws + threadIdx.x * BLOCK_WAVES);
 }
 
 std::tuple<torch::Tensor, torch::Tensor> quantize_fwd(torch::Tensor x,
                                                       torch::Tensor centers,
                                                       double sigma) {
-  CHECK_CUDA_CONTIG(x);
-  CHECK_CUDA_CONTIG(centers);
-  TORCH_CHECK(x.scalar_type() == torch::kFloat32, "quantize: x must be fp32");
+  check_arg(x, "quantize_fwd: x", torch::kFloat32);
+  check_arg(centers, "quantize_fwd: centers", torch::kFloat32);
   int L = centers.numel();
   TORCH_CHECK(L <= MAX_L, "quantize: at most ", MAX_L, " centers");
   auto qbar = torch::empty_like(x);
   auto symbols = torch::empty(x.sizes(), x.options().dtype(torch::kInt64));
   int64_t n = x.numel();
-  int block = 256;
-  int grid = std::min<int64_t>((n + block - 1) / block, 4096);
-  hipLaunchKernelGGL(quantize_fwd_kernel, dim3(grid), dim3(block), 0,
+  hipLaunchKernelGGL(quantize_fwd_kernel, dim3(ew_grid(n)),
+                     dim3(BLOCK_THREADS), 0,
                      at::cuda::getCurrentCUDAStream(),
                      x.data_ptr<float>(), centers.data_ptr<float>(),
                      qbar.data_ptr<float>(), symbols.data_ptr<int64_t>(),
@@ -147,17 +137,18 @@ std::tuple<torch::Tensor, torch::Tensor> quantize_bwd(torch::Tensor g,
                                                       torch::Tensor x,
                                                       torch::Tensor centers,
                                                       double sigma) {
-  CHECK_CUDA_CONTIG(g);
-  CHECK_CUDA_CONTIG(x);
-  CHECK_CUDA_CONTIG(centers);
+  check_arg(x, "quantize_bwd: x", torch::kFloat32);
+  check_arg_shape(g, "quantize_bwd: g", torch::kFloat32, x.sizes());
+  check_arg(centers, "quantize_bwd: centers", torch::kFloat32);
   int L = centers.numel();
+  TORCH_CHECK(L <= MAX_L, "quantize: at most ", MAX_L, " centers");
   auto gx = torch::empty_like(x);
   int64_t n = x.numel();
-  int block = 256;
-  int grid = std::min<int64_t>((n + block - 1) / block, 2048);
+  // the cap sets the number of partials, and so the order of the sum
+  int grid = ew_grid(n, 2048);
   // (grid, L) per-block partials, reduced with one ordered sum
   auto gcp = torch::empty({grid, L}, centers.options());
-  hipLaunchKernelGGL(quantize_bwd_kernel, dim3(grid), dim3(block), 0,
+  hipLaunchKernelGGL(quantize_bwd_kernel, dim3(grid), dim3(BLOCK_THREADS), 0,
                      at::cuda::getCurrentCUDAStream(),
                      g.data_ptr<float>(), x.data_ptr<float>(),
                      centers.data_ptr<float>(), gx.data_ptr<float>(),

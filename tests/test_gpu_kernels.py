@@ -40,59 +40,6 @@ def test_mfma_16x16x32_layout(dev):
     torch.testing.assert_close(C, expect, rtol=1e-3, atol=1e-3)
 
 
-# ---------------------------------------------------------------- quantizer
-
-def test_quantize_fwd_matches_ref(dev):
-    torch.manual_seed(1)
-    x = torch.randn(1, 32, 40, 120, device=dev) * 2
-    centers = torch.linspace(-2, 2, 6, device=dev)
-    qbar, symbols = ops.quantize(x, centers)
-    qref, _, qhard, sref = ref.quantize_ref(x, centers)
-    assert torch.equal(symbols, sref)
-    torch.testing.assert_close(qbar, qref, rtol=1e-5, atol=1e-6)
-
-
-def test_quantize_bwd_matches_autograd(dev):
-    torch.manual_seed(2)
-    x = torch.randn(1, 8, 10, 12, device=dev, requires_grad=True)
-    centers = torch.linspace(-2, 2, 6, device=dev, requires_grad=True)
-    qbar, _ = ops.quantize(x, centers)
-    g = torch.randn_like(qbar)
-    gx, gc = torch.autograd.grad(qbar, (x, centers), g)
-
-    x2 = x.detach().clone().requires_grad_(True)
-    c2 = centers.detach().clone().requires_grad_(True)
-    qref, _, _, _ = ref.quantize_ref(x2, c2)
-    gx2, gc2 = torch.autograd.grad(qref, (x2, c2), g)
-    torch.testing.assert_close(gx, gx2, rtol=1e-4, atol=1e-6)
-    torch.testing.assert_close(gc, gc2, rtol=1e-4, atol=1e-4)
-
-
-# ---------------------------------------------------------------- bitcost
-
-def test_bitcost_fwd_matches_ref(dev):
-    torch.manual_seed(3)
-    logits = torch.randn(1, 6, 32, 40, 60, device=dev)
-    symbols = torch.randint(0, 6, (1, 32, 40, 60), device=dev)
-    bits = ops.bitcost_ce(logits, symbols)
-    expect = ref.bitcost_ce_ref(logits, symbols)
-    torch.testing.assert_close(bits, expect, rtol=1e-5, atol=1e-5)
-
-
-def test_bitcost_bwd_matches_autograd(dev):
-    torch.manual_seed(4)
-    logits = torch.randn(1, 6, 8, 10, 12, device=dev, requires_grad=True)
-    symbols = torch.randint(0, 6, (1, 8, 10, 12), device=dev)
-    bits = ops.bitcost_ce(logits, symbols)
-    g = torch.rand_like(bits)
-    (gl,) = torch.autograd.grad(bits, logits, g)
-
-    l2 = logits.detach().clone().requires_grad_(True)
-    expect = ref.bitcost_ce_ref(l2, symbols)
-    (gl2,) = torch.autograd.grad(expect, l2, g)
-    torch.testing.assert_close(gl, gl2, rtol=1e-4, atol=1e-6)
-
-
 # ---------------------------------------------------------------- integration
 
 def test_full_train_step_on_gpu(dev):
@@ -114,67 +61,6 @@ def test_full_train_step_on_gpu(dev):
         x, y = gen.next_batch()
         loss, bpp = tr.train_step(x, y)
         assert torch.isfinite(loss) and torch.isfinite(bpp)
-
-
-def test_heatmap_mask_matches_eager(dev):
-    from dsin_amd import ops
-    from dsin_amd.ops import reference as ref
-    torch.manual_seed(5)
-    for dtype in (torch.float32, torch.bfloat16):
-        b = torch.randn(2, 33, 10, 12, device=dev, dtype=dtype) * 3
-        b1 = b.clone().requires_grad_(True)
-        z, h3 = ops.heatmap_mask(b1)
-        b2 = b.clone().float().requires_grad_(True)
-        h3r = ref.heatmap3d_ref(b2)
-        zr = h3r * b2[:, 1:]
-        torch.testing.assert_close(z.float(), zr, rtol=2e-2, atol=2e-2)
-        torch.testing.assert_close(h3.float(), h3r, rtol=2e-2, atol=2e-2)
-        gz = torch.randn_like(zr)
-        gh = torch.randn_like(h3r)
-        (z.float() * gz + h3.float() * gh).sum().backward()
-        (zr * gz + h3r * gh).sum().backward()
-        torch.testing.assert_close(b1.grad.float(), b2.grad, rtol=5e-2,
-                                   atol=5e-2)
-
-
-def test_l1_mean_matches_eager(dev):
-    from dsin_amd import ops
-    torch.manual_seed(6)
-    x = torch.randn(3, 4, 33, 47, device=dev) * 50
-    y = (torch.randn(3, 4, 33, 47, device=dev) * 50).to(torch.bfloat16)
-    x1 = x.clone().requires_grad_(True)
-    y1 = y.clone().requires_grad_(True)
-    m = ops.l1_mean_per_image(x1, y1)
-    x2 = x.clone().requires_grad_(True)
-    y2 = y.clone().requires_grad_(True)
-    mr = (y2.float() - x2).abs().mean(dim=(1, 2, 3))
-    torch.testing.assert_close(m, mr, rtol=1e-4, atol=1e-4)
-    g = torch.randn(3, device=dev)
-    (m * g).sum().backward()
-    (mr * g).sum().backward()
-    torch.testing.assert_close(x1.grad, x2.grad, rtol=1e-3, atol=1e-3)
-    torch.testing.assert_close(y1.grad.float(), y2.grad.float(), rtol=1e-2,
-                               atol=1e-2)
-
-
-def test_rate_terms_match_eager(dev):
-    from dsin_amd import ops
-    torch.manual_seed(7)
-    bc = (torch.rand(1, 32, 40, 60, device=dev) * 3).requires_grad_(True)
-    heat = torch.rand(1, 32, 40, 60, device=dev).to(torch.bfloat16)
-    heat.requires_grad_(True)
-    hr, hm = ops.rate_terms(bc, heat)
-    bc2 = bc.detach().clone().requires_grad_(True)
-    h2 = heat.detach().clone().requires_grad_(True)
-    hr2 = bc2.mean()
-    hm2 = (bc2 * h2).mean()
-    torch.testing.assert_close(hr, hr2, rtol=1e-4, atol=1e-5)
-    torch.testing.assert_close(hm, hm2, rtol=1e-3, atol=1e-4)
-    (2.0 * hr + 3.0 * hm).backward()
-    (2.0 * hr2 + 3.0 * hm2).backward()
-    torch.testing.assert_close(bc.grad, bc2.grad, rtol=1e-3, atol=1e-6)
-    torch.testing.assert_close(heat.grad.float(), h2.grad.float(), rtol=1e-2,
-                               atol=1e-5)
 
 
 def test_codec_roundtrip_on_gpu(dev):
@@ -269,37 +155,6 @@ def test_step_bitwise_determinism(dev):
 
 # ---------------------------------------------------------------- fused Adam
 
-def test_fused_adam_matches_tf_semantics(dev):
-    """FusedAdam vs a hand-rolled TF AdamOptimizer reference:
-    p -= lr sqrt(1-b2^t)/(1-b1^t) * m / (sqrt(v) + eps)."""
-    from dsin_amd.ops.adam import FusedAdam
-    torch.manual_seed(0)
-    shapes = [(3, 5), (7,), (2, 3, 4)]
-    init = [torch.randn(s, device=dev) for s in shapes]
-    params = [torch.nn.Parameter(t.clone()) for t in init]
-    opt = FusedAdam(params, lr=1e-2)
-
-    ref_p = [t.clone() for t in init]
-    ref_m = [torch.zeros_like(t) for t in init]
-    ref_v = [torch.zeros_like(t) for t in init]
-    b1, b2, eps, lr = 0.9, 0.999, 1e-8, 1e-2
-
-    for t_step in range(1, 4):
-        grads = [torch.randn_like(t) for t in init]
-        opt.zero_grad()
-        for p, g in zip(params, grads):
-            p.grad = g.clone()   # autograd "steals" grads in the new flow
-        opt.gather_grads()
-        opt.step()
-        for i in range(len(ref_p)):
-            ref_m[i] = b1 * ref_m[i] + (1 - b1) * grads[i]
-            ref_v[i] = b2 * ref_v[i] + (1 - b2) * grads[i] ** 2
-            corr = lr * (1 - b2 ** t_step) ** 0.5 / (1 - b1 ** t_step)
-            ref_p[i] -= corr * ref_m[i] / (ref_v[i].sqrt() + eps)
-        for p, r in zip(params, ref_p):
-            torch.testing.assert_close(p.data, r, rtol=1e-5, atol=1e-6)
-
-
 def test_fused_adam_in_trainer(dev):
     import os
     from dsin_amd import config as cm
@@ -321,57 +176,6 @@ def test_fused_adam_in_trainer(dev):
     loss, bpp = tr.train_step(x, y)
     assert torch.isfinite(loss)
     assert not torch.equal(w_before, model.encoder.h1.conv.weight)
-
-
-# ---------------------------------------------------------------- fused BN
-
-def test_bn_act_matches_torch(dev):
-    from dsin_amd.ops.bn import batch_norm_act
-    torch.manual_seed(0)
-    bn1 = torch.nn.BatchNorm2d(32, eps=1e-5, momentum=0.1).to(dev)
-    bn2 = torch.nn.BatchNorm2d(32, eps=1e-5, momentum=0.1).to(dev)
-    with torch.no_grad():
-        bn2.weight.copy_(bn1.weight)
-        bn2.bias.copy_(bn1.bias)
-        g = torch.rand(32, device=dev) + 0.5
-        bn1.weight.copy_(g); bn2.weight.copy_(g)
-        b = torch.randn(32, device=dev) * 0.3
-        bn1.bias.copy_(b); bn2.bias.copy_(b)
-    x = (torch.randn(2, 32, 20, 24, device=dev) * 2 + 1).to(torch.bfloat16)
-    x1 = x.clone().requires_grad_(True)
-    y1 = batch_norm_act(x1, bn1, training=True, act=1)
-    x2 = x.float().clone().requires_grad_(True)
-    y2 = torch.relu(torch.nn.functional.batch_norm(
-        x2, bn2.running_mean, bn2.running_var, bn2.weight, bn2.bias, True,
-        0.1, 1e-5))
-    torch.testing.assert_close(y1.float(), y2, rtol=0.05, atol=0.05)
-    torch.testing.assert_close(bn1.running_mean, bn2.running_mean,
-                               rtol=1e-2, atol=1e-2)
-    torch.testing.assert_close(bn1.running_var, bn2.running_var,
-                               rtol=1e-2, atol=1e-2)
-    gr = torch.randn_like(y2)
-    y1.backward(gr.to(y1.dtype))
-    y2.backward(gr)
-    torch.testing.assert_close(x1.grad.float(), x2.grad, rtol=0.1, atol=0.1)
-    torch.testing.assert_close(bn1.weight.grad, bn2.weight.grad,
-                               rtol=0.05, atol=0.3)
-    torch.testing.assert_close(bn1.bias.grad, bn2.bias.grad,
-                               rtol=0.05, atol=0.3)
-
-
-def test_bn_eval_mode(dev):
-    from dsin_amd.ops.bn import batch_norm_act
-    torch.manual_seed(1)
-    bn = torch.nn.BatchNorm2d(16).to(dev)
-    with torch.no_grad():
-        bn.running_mean.uniform_(-1, 1)
-        bn.running_var.uniform_(0.5, 2)
-    x = torch.randn(1, 16, 8, 12, device=dev).to(torch.bfloat16)
-    y = batch_norm_act(x, bn, training=False, act=0)
-    yr = torch.nn.functional.batch_norm(
-        x.float(), bn.running_mean, bn.running_var, bn.weight, bn.bias,
-        False, 0.1, bn.eps)
-    torch.testing.assert_close(y.float(), yr, rtol=0.05, atol=0.05)
 
 
 def test_graph_capture_matches_eager(dev):
