@@ -1,7 +1,8 @@
 """Side-information patch search driver.
 
-Batch wrapper over the single-image NCC search op (ops.ncc_search): for each
-image in the batch, match every non-overlapping (ph, pw) patch of x_dec
+Module over the batched NCC search op (ops.ncc_search_batch, one call for
+the N images; on the GPU one launch per pipeline stage): for each image in
+the batch, match every non-overlapping (ph, pw) patch of x_dec
 against all locations of the DECODED side image y_dec (Pearson correlation on
 fixed-normalized, H1H2H3-decorrelated values, weighted by a Gaussian location
 prior), then gather the winning patches FROM THE ORIGINAL y and scatter them
@@ -34,10 +35,7 @@ class SiFinder(torch.nn.Module):
     def forward(self, x_dec: torch.Tensor, y_orig: torch.Tensor,
                 y_dec: torch.Tensor) -> torch.Tensor:
         """x_dec, y_orig, y_dec: (N, 3, H, W) -> y_syn (N, 3, H, W)."""
-        outs = []
-        for n in range(x_dec.shape[0]):
-            y_syn, _, _ = ops.ncc_search(x_dec[n], y_dec[n], y_orig[n],
-                                         self.ph, self.pw, self.use_mask,
-                                         l2lab=self.l2lab)
-            outs.append(y_syn)
-        return torch.stack(outs).to(x_dec.dtype)
+        y_syn, _, _ = ops.ncc_search_batch(x_dec, y_dec, y_orig, self.ph,
+                                           self.pw, self.use_mask,
+                                           l2lab=self.l2lab)
+        return y_syn.to(x_dec.dtype)

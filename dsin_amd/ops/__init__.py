@@ -257,12 +257,57 @@ def ncc_search(x_dec: torch.Tensor, y_dec: torch.Tensor, y_orig: torch.Tensor,
     sync); on the CPU both run the torch reference in fp32."""
     check_ncc_inputs(x_dec, y_dec, y_orig, ph, pw, use_mask)
     if x_dec.is_cuda:
-        fn = _require_ext("ncc_search_l2lab" if l2lab else "ncc_search")
-        y_syn, rows, cols = fn(x_dec.contiguous().float(), y_dec.contiguous().float(),
-                               y_orig.contiguous().float(), ph, pw, use_mask)
-        return y_syn, rows, cols
+        # the batch of one: the kernels have no other form
+        y_syn, rows, cols = _ncc_search_ext(x_dec[None], y_dec[None],
+                                            y_orig[None], ph, pw, use_mask,
+                                            l2lab)
+        return y_syn[0], rows[0], cols[0]
     return ref.ncc_search_ref(x_dec.float(), y_dec.float(), y_orig.float(),
                               ph, pw, use_mask, l2lab=l2lab)
+
+
+def _ncc_search_ext(x_dec, y_dec, y_orig, ph, pw, use_mask, l2lab):
+    """(B,3,H,W) checked device tensors through the extension."""
+    fn = _require_ext("ncc_search_l2lab" if l2lab else "ncc_search")
+    return fn(x_dec.contiguous().float(), y_dec.contiguous().float(),
+              y_orig.contiguous().float(), ph, pw, use_mask)
+
+
+def check_ncc_batch_inputs(x_dec, y_dec, y_orig, ph: int, pw: int,
+                           use_mask: bool):
+    """The batch form of check_ncc_inputs: rank, B >= 1 and one shape here,
+    the per-image geometry there."""
+    if x_dec.dim() != 4 or x_dec.shape[0] < 1 or x_dec.shape[1] != 3:
+        raise ValueError(f"ncc_search_batch: images must be (B, 3, H, W) "
+                         f"with B >= 1, got {tuple(x_dec.shape)}")
+    if x_dec.shape != y_dec.shape or x_dec.shape != y_orig.shape:
+        raise ValueError(
+            f"ncc_search_batch: the three batches must share one shape, got "
+            f"{tuple(x_dec.shape)}, {tuple(y_dec.shape)}, "
+            f"{tuple(y_orig.shape)}")
+    check_ncc_inputs(x_dec[0], y_dec[0], y_orig[0], ph, pw, use_mask)
+
+
+@torch.no_grad()
+def ncc_search_batch(x_dec: torch.Tensor, y_dec: torch.Tensor,
+                     y_orig: torch.Tensor, ph: int, pw: int,
+                     use_mask: bool = True, l2lab: bool = False
+                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """SI search of B >= 1 images of one size: (B,3,H,W)x3 -> (y_syn
+    (B,3,H,W), rows (B,P), cols (B,P)); image b of the result is what
+    ncc_search returns for image b, bit for bit. On the GPU the B images
+    share one launch per pipeline stage and one allocation per intermediate
+    (B times the grid, the launches of one image, no host sync); on the CPU
+    the torch reference runs per image."""
+    check_ncc_batch_inputs(x_dec, y_dec, y_orig, ph, pw, use_mask)
+    if x_dec.is_cuda:
+        return _ncc_search_ext(x_dec, y_dec, y_orig, ph, pw, use_mask, l2lab)
+    outs = [ref.ncc_search_ref(x_dec[b].float(), y_dec[b].float(),
+                               y_orig[b].float(), ph, pw, use_mask,
+                               l2lab=l2lab)
+            for b in range(x_dec.shape[0])]
+    y_syn, rows, cols = (torch.stack(t) for t in zip(*outs))
+    return y_syn, rows, cols
 
 
 @torch.no_grad()

@@ -29,8 +29,19 @@ constexpr int NCC_TJ2 = 64;  // v2 col tile: 2 j-waves x 32 — the y window
                              // L1 with two co-resident blocks; the other 2
                              // waves take the other 4-row output group
 
+// Every kernel below except ncc_offsets_kernel runs B images of one geometry
+// in one launch. The image index comes from the grid (blockIdx.y, or folded
+// into blockIdx.z in the two main kernels), is uniform over the block and is
+// used once, at entry, to move the base pointers to this image, in 64-bit
+// arithmetic: B*3*H*W can pass 2^31. Per-image strides:
+//   tx, ty, y_orig, y_syn          3*H*W
+//   psum, psum2, best, rows, cols  P
+//   s1, s2                         H*Wc
+//   sy, sy2                        Hc*Wc
+// Everything after the entry indexes within one image, as for B = 1.
+
 // ---------------------------------------------------------------- stage 0
-// Offset tables, computed once per call:
+// Offset tables, computed once per call (geometry only, shared by the images):
 //   aoffs[k] = element offset of flat-k within the (3,H,W) image relative to
 //              a patch origin (k = (c*ph + a)*pw + b)
 //   koffs[k] = element offset of flat-k within the LDS y-window image
@@ -51,6 +62,8 @@ __global__ void ncc_offsets_kernel(unsigned int* __restrict__ aoffs,
 
 __global__ void transform_kernel(const float* __restrict__ img,
                                  bf16* __restrict__ out, long long hw) {
+  img += (long long)blockIdx.y * 3 * hw;
+  out += (long long)blockIdx.y * 3 * hw;
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long stride = (long long)gridDim.x * blockDim.x;
   for (; i < hw; i += stride) {
@@ -80,6 +93,8 @@ __device__ __forceinline__ float lab_f(float t) {
 
 __global__ void lab_transform_kernel(const float* __restrict__ img,
                                      bf16* __restrict__ out, long long hw) {
+  img += (long long)blockIdx.y * 3 * hw;
+  out += (long long)blockIdx.y * 3 * hw;
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long stride = (long long)gridDim.x * blockDim.x;
   for (; i < hw; i += stride) {
@@ -107,6 +122,10 @@ __global__ void patch_stats_kernel(const bf16* __restrict__ tx,
                                    float* __restrict__ psum2,
                                    int H, int W, int ph, int pw, int gw,
                                    int K) {
+  const int P = gridDim.x;  // grid (P, B)
+  tx += (long long)blockIdx.y * 3 * H * W;
+  psum += (long long)blockIdx.y * P;
+  psum2 += (long long)blockIdx.y * P;
   int p = blockIdx.x;
   long long base = (long long)((p / gw) * ph) * W + (p % gw) * pw;
   float s = 0.f, s2 = 0.f;
@@ -130,6 +149,9 @@ __global__ void ysum_row_kernel(const bf16* __restrict__ ty,
                                 int H, int W, int pw, int Wc) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long total = (long long)H * Wc;
+  ty += (long long)blockIdx.y * 3 * H * W;
+  s1 += (long long)blockIdx.y * total;
+  s2 += (long long)blockIdx.y * total;
   if (i >= total) return;
   int r = i / Wc, j = i % Wc;
   float a = 0.f, b = 0.f;
@@ -152,6 +174,11 @@ __global__ void ysum_col_kernel(const float* __restrict__ s1,
                                 int Hc, int Wc, int ph) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long total = (long long)Hc * Wc;
+  const long long rows_in = (long long)(Hc + ph - 1) * Wc;  // H*Wc
+  s1 += (long long)blockIdx.y * rows_in;
+  s2 += (long long)blockIdx.y * rows_in;
+  sy += (long long)blockIdx.y * total;
+  sy2 += (long long)blockIdx.y * total;
   if (i >= total) return;
   int r = i / Wc, j = i % Wc;
   float a = 0.f, b = 0.f;
@@ -306,6 +333,36 @@ __device__ __forceinline__ void ncc_epilogue_row(
   }
 }
 
+// The main kernels' grid is (column tiles, row tiles, B * patch tiles) with
+// the image the slowest part of z: the workgroups of one image stay adjacent
+// in block order and keep its ty hot in L2/L1, as for one image. Moves the
+// per-image pointers to this block's image and returns its first patch.
+// zmagic = 2^32 / ptiles + 1 comes from the host: (z * zmagic) >> 32 equals
+// z / ptiles for every z, ptiles < 2^16 (the error term z * (zmagic * ptiles
+// - 2^32) stays below 2^32), which is all gridDim.z admits. Chosen by
+// measurement: with a plain division here the one-image v1 L2 search ran 0.9
+// to 1.7 % slower than before the batch, with this form 0.5 to 0.9 %
+// (profiles/r15_ncc_batch.md; the mechanism is not established).
+__device__ __forceinline__ int ncc_enter_image(
+    unsigned long long zmagic, int H, int W, int P, int Hc, int Wc,
+    const bf16* __restrict__& tx,
+    const bf16* __restrict__& ty, const float* __restrict__& psum,
+    const float* __restrict__& psum2, const float* __restrict__& sy,
+    const float* __restrict__& sy2, unsigned long long* __restrict__& best) {
+  const int ptiles = (P + NCC_TP - 1) / NCC_TP;
+  const int b = (int)(((unsigned long long)blockIdx.z * zmagic) >> 32);
+  const long long img = (long long)b * 3 * H * W;
+  const long long loc = (long long)b * Hc * Wc;
+  tx += img;
+  ty += img;
+  psum += (long long)b * P;
+  psum2 += (long long)b * P;
+  sy += loc;
+  sy2 += loc;
+  best += (long long)b * P;
+  return (blockIdx.z - b * ptiles) * NCC_TP;
+}
+
 // Reduces the running keys across the 32 lanes of each half-wave (distinct
 // columns, the same 16 patches) and sends one atomicMax per patch.
 __device__ __forceinline__ void ncc_merge_best(
@@ -347,9 +404,10 @@ void ncc_main_kernel(const bf16* __restrict__ tx, const bf16* __restrict__ ty,
                      const float* __restrict__ psum2,
                      const float* __restrict__ sy,
                      const float* __restrict__ sy2,
-                     unsigned long long* __restrict__ best,  // (P,)
+                     unsigned long long* __restrict__ best,  // (B, P)
                      int H, int W, int ph, int pw, int gw, int P,
-                     int Hc, int Wc, int use_mask) {
+                     int Hc, int Wc, int use_mask,
+                     unsigned long long zmagic) {
   const int K = 3 * ph * pw;
   const NccLdsV1 lds = ncc_lds_v1(ph, pw);
   const int KP = lds.KP, YR = lds.YR, YC = lds.YC, YCP = lds.YCP;
@@ -366,7 +424,8 @@ void ncc_main_kernel(const bf16* __restrict__ tx, const bf16* __restrict__ ty,
   const int wid = tid >> 6;
   const int j0 = blockIdx.x * NCC_TJ;
   const int i0 = blockIdx.y * NCC_TI;
-  const int p0 = blockIdx.z * NCC_TP;
+  const int p0 = ncc_enter_image(zmagic, H, W, P, Hc, Wc, tx, ty, psum,
+                                 psum2, sy, sy2, best);
 
   // ---- stage A tile (32 patches x K), y window, koffs, patch stats ----
   for (int k = tid; k < KP; k += 256) Ko[k] = (k < K) ? koffs[k] : 0;
@@ -464,9 +523,10 @@ void ncc_main_v2_kernel(const bf16* __restrict__ tx,
                         const float* __restrict__ psum2,
                         const float* __restrict__ sy,
                         const float* __restrict__ sy2,
-                        unsigned long long* __restrict__ best,  // (P,)
+                        unsigned long long* __restrict__ best,  // (B, P)
                         int H, int W, int ph, int pw, int gw, int P,
-                        int Hc, int Wc, int use_mask) {
+                        int Hc, int Wc, int use_mask,
+                        unsigned long long zmagic) {
   const int K = 3 * ph * pw;
   const NccLdsV2 lds = ncc_lds_v2(ph, pw);
   const int KP = lds.KP;
@@ -481,7 +541,8 @@ void ncc_main_v2_kernel(const bf16* __restrict__ tx,
   const int wid = tid >> 6;
   const int j0 = blockIdx.x * NCC_TJ2;
   const int i0 = blockIdx.y * NCC_TI;
-  const int p0 = blockIdx.z * NCC_TP;
+  const int p0 = ncc_enter_image(zmagic, H, W, P, Hc, Wc, tx, ty, psum,
+                                 psum2, sy, sy2, best);
 
   ncc_stage_pstat<L2>(Pstat, tid, p0, P, psum, psum2, K, ph, pw, gw);
 
@@ -612,11 +673,12 @@ void ncc_main_v2_kernel(const bf16* __restrict__ tx,
 #define NCC_MAIN_ARGS                                                        \
   const bf16*, const bf16*, const unsigned int*, const unsigned short*, \
       const float*, const float*, const float*, const float*,               \
-      unsigned long long*, int, int, int, int, int, int, int, int, int
+      unsigned long long*, int, int, int, int, int, int, int, int, int, \
+      unsigned long long
 #define NCC_MAIN_V2_ARGS                                                   \
   const bf16*, const bf16*, const unsigned int*, const float*,        \
       const float*, const float*, const float*, unsigned long long*, int, \
-      int, int, int, int, int, int, int, int
+      int, int, int, int, int, int, int, int, unsigned long long
 template __global__ void ncc_main_kernel<false>(NCC_MAIN_ARGS);
 template __global__ void ncc_main_kernel<true>(NCC_MAIN_ARGS);
 template __global__ void ncc_main_v2_kernel<false>(NCC_MAIN_V2_ARGS);
@@ -633,6 +695,11 @@ __global__ void scatter_kernel(const unsigned long long* __restrict__ best,
                                long long* __restrict__ cols,
                                int H, int W, int ph, int pw, int gw, int P,
                                int Wc) {
+  best += (long long)blockIdx.y * P;
+  rows += (long long)blockIdx.y * P;
+  cols += (long long)blockIdx.y * P;
+  y_orig += (long long)blockIdx.y * 3 * H * W;
+  y_syn += (long long)blockIdx.y * 3 * H * W;
   int p = blockIdx.x;
   unsigned int idx = ~(unsigned int)(best[p] & 0xFFFFFFFFull);
   int bi = idx / Wc, bj = idx % Wc;

@@ -22,11 +22,20 @@
 // the score is the squared distance sum_x2 - 2*xy + sum_y2 times the same
 // prior, and the winner is the argmin, first index on ties. Same pipeline;
 // only the transform kernel and the main-kernel instantiation differ.
+//
+// The batch is the only form below the Python API: B images of one geometry
+// go through one launch per stage (one image is B = 1), every intermediate is
+// one allocation with a leading B, and the image index is a grid dimension
+// (strides at the head of ncc_kernels.h). Scores, keys and ties are per image
+// and do not depend on B.
 
 #include "common.h"
 #include "ncc_kernels.h"
 
 namespace dsin {
+
+// gridDim.y and gridDim.z hold at most 65535 blocks
+constexpr int64_t NCC_GRID_YZ_MAX = 65535;
 
 template <bool L2>
 static std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search_impl(
@@ -35,13 +44,26 @@ static std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search_impl(
   CHECK_CUDA_CONTIG(x_dec);
   CHECK_CUDA_CONTIG(y_dec);
   CHECK_CUDA_CONTIG(y_orig);
-  TORCH_CHECK(x_dec.dim() == 3 && x_dec.size(0) == 3, "x_dec must be (3,H,W)");
+  TORCH_CHECK(x_dec.dim() == 4 && x_dec.size(0) >= 1 && x_dec.size(1) == 3,
+              "x_dec must be (B,3,H,W) with B >= 1");
   TORCH_CHECK(x_dec.sizes() == y_dec.sizes() && x_dec.sizes() == y_orig.sizes(),
               "x/y size mismatch (equal sizes required)");
   const int ph = (int)ph_, pw = (int)pw_;
-  const int H = (int)x_dec.size(1), W = (int)x_dec.size(2);
+  const int64_t B = x_dec.size(0);
+  const int H = (int)x_dec.size(2), W = (int)x_dec.size(3);
   TORCH_CHECK(H % ph == 0 && W % pw == 0, "image must tile by the patch size");
   const int gh = H / ph, gw = W / pw, P = gh * gw;
+  // The image is blockIdx.y of the small kernels and the slow part of the
+  // main kernels' blockIdx.z, next to the patch tiles.
+  const int64_t ptiles = (P + NCC_TP - 1) / NCC_TP;
+  const int64_t maxB = NCC_GRID_YZ_MAX / ptiles;
+  // blockIdx.z / ptiles as a multiply and a shift (ncc_enter_image)
+  const unsigned long long zmagic =
+      (1ull << 32) / (unsigned long long)ptiles + 1;
+  TORCH_CHECK(B <= maxB, "ncc_search: a batch of ", B, " images of ", P,
+              " patches needs ", B * ptiles, " blocks in grid z; at most ",
+              NCC_GRID_YZ_MAX, " fit, so the largest batch at this geometry is ",
+              maxB);
   const int Hc = H - ph + 1, Wc = W - pw + 1;
   const int K = 3 * ph * pw;
   // v2 (pw % 8 == 0, the default geometry): k-sliced LDS A-tile + direct
@@ -64,41 +86,51 @@ static std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search_impl(
                      (unsigned short*)koffs.data_ptr(), H, W, ph, pw, YR, YCP,
                      K);
 
-  auto t_x = torch::empty({3, H, W}, optsF.dtype(torch::kBFloat16));
-  // +192 elements of tail slack: the v2 kernel's invalid-column vector
-  // loads may overshoot the last row (values discarded)
-  auto t_y = torch::empty({(int64_t)3 * H * W + 192},
+  const unsigned int nb = (unsigned int)B;
+  // grid of a one-thread-per-element stage: x over the elements of one
+  // image, y the image
+  const auto grid_img = [nb](int64_t n) {
+    return dim3(grid1d(n, 256).x, nb);
+  };
+
+  auto t_x = torch::empty({B, 3, H, W}, optsF.dtype(torch::kBFloat16));
+  // The images lie back to back, then 192 elements of tail slack: the v2
+  // kernel's invalid-column vector loads may overshoot the last row of an
+  // image. Past image b < B-1 they land in image b+1, past the last image in
+  // the slack; either way the jvalid select of the epilogue discards what
+  // they read, so the slack is needed once, not per image.
+  auto t_y = torch::empty({B * 3 * H * W + 192},
                           optsF.dtype(torch::kBFloat16));
   int64_t hw = (int64_t)H * W;
   const auto transform = L2 ? lab_transform_kernel : transform_kernel;
-  hipLaunchKernelGGL(transform, grid1d(hw, 256), dim3(256), 0, stream,
+  hipLaunchKernelGGL(transform, grid_img(hw), dim3(256), 0, stream,
                      x_dec.data_ptr<float>(), (bf16*)t_x.data_ptr(), hw);
-  hipLaunchKernelGGL(transform, grid1d(hw, 256), dim3(256), 0, stream,
+  hipLaunchKernelGGL(transform, grid_img(hw), dim3(256), 0, stream,
                      y_dec.data_ptr<float>(), (bf16*)t_y.data_ptr(), hw);
 
-  auto psum = torch::empty({P}, optsF);
-  auto psum2 = torch::empty({P}, optsF);
-  hipLaunchKernelGGL(patch_stats_kernel, dim3(P), dim3(64), 0, stream,
+  auto psum = torch::empty({B, P}, optsF);
+  auto psum2 = torch::empty({B, P}, optsF);
+  hipLaunchKernelGGL(patch_stats_kernel, dim3(P, nb), dim3(64), 0, stream,
                      (const bf16*)t_x.data_ptr(),
                      (const unsigned int*)aoffs.data_ptr(),
                      psum.data_ptr<float>(), psum2.data_ptr<float>(), H, W, ph,
                      pw, gw, K);
 
-  auto s1 = torch::empty({(int64_t)H * Wc}, optsF);
-  auto s2 = torch::empty({(int64_t)H * Wc}, optsF);
-  auto sy = torch::empty({(int64_t)Hc * Wc}, optsF);
-  auto sy2 = torch::empty({(int64_t)Hc * Wc}, optsF);
-  hipLaunchKernelGGL(ysum_row_kernel, grid1d((int64_t)H * Wc, 256), dim3(256),
+  auto s1 = torch::empty({B, (int64_t)H * Wc}, optsF);
+  auto s2 = torch::empty({B, (int64_t)H * Wc}, optsF);
+  auto sy = torch::empty({B, (int64_t)Hc * Wc}, optsF);
+  auto sy2 = torch::empty({B, (int64_t)Hc * Wc}, optsF);
+  hipLaunchKernelGGL(ysum_row_kernel, grid_img((int64_t)H * Wc), dim3(256),
                      0, stream, (const bf16*)t_y.data_ptr(),
                      s1.data_ptr<float>(), s2.data_ptr<float>(), H, W, pw, Wc);
-  hipLaunchKernelGGL(ysum_col_kernel, grid1d((int64_t)Hc * Wc, 256), dim3(256),
+  hipLaunchKernelGGL(ysum_col_kernel, grid_img((int64_t)Hc * Wc), dim3(256),
                      0, stream, s1.data_ptr<float>(), s2.data_ptr<float>(),
                      sy.data_ptr<float>(), sy2.data_ptr<float>(), Hc, Wc, ph);
 
-  auto best = torch::zeros({P}, optsF.dtype(torch::kInt64));  // u64 keys
+  auto best = torch::zeros({B, P}, optsF.dtype(torch::kInt64));  // u64 keys
   const int tj = v2 ? NCC_TJ2 : NCC_TJ;
   dim3 grid((Wc + tj - 1) / tj, (Hc + NCC_TI - 1) / NCC_TI,
-            (P + NCC_TP - 1) / NCC_TP);
+            (unsigned int)(B * ptiles));
   if (v2) {
     hipLaunchKernelGGL(ncc_main_v2_kernel<L2>, grid, dim3(256), lds, stream,
                        (const bf16*)t_x.data_ptr(),
@@ -107,7 +139,7 @@ static std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search_impl(
                        psum.data_ptr<float>(), psum2.data_ptr<float>(),
                        sy.data_ptr<float>(), sy2.data_ptr<float>(),
                        (unsigned long long*)best.data_ptr(), H, W, ph, pw,
-                       gw, P, Hc, Wc, use_mask ? 1 : 0);
+                       gw, P, Hc, Wc, use_mask ? 1 : 0, zmagic);
   } else {
     hipLaunchKernelGGL(ncc_main_kernel<L2>, grid, dim3(256), lds, stream,
                        (const bf16*)t_x.data_ptr(),
@@ -117,7 +149,7 @@ static std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search_impl(
                        psum.data_ptr<float>(), psum2.data_ptr<float>(),
                        sy.data_ptr<float>(), sy2.data_ptr<float>(),
                        (unsigned long long*)best.data_ptr(), H, W, ph, pw,
-                       gw, P, Hc, Wc, use_mask ? 1 : 0);
+                       gw, P, Hc, Wc, use_mask ? 1 : 0, zmagic);
   }
   // a refused launch (e.g. the dynamic LDS request) would leave `best` zero,
   // and scatter_kernel would decode index 0xFFFFFFFF from it
@@ -130,9 +162,9 @@ static std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search_impl(
   }
 
   auto y_syn = torch::empty_like(y_orig);
-  auto rows = torch::empty({P}, optsF.dtype(torch::kInt64));
-  auto cols = torch::empty({P}, optsF.dtype(torch::kInt64));
-  hipLaunchKernelGGL(scatter_kernel, dim3(P), dim3(256), 0, stream,
+  auto rows = torch::empty({B, P}, optsF.dtype(torch::kInt64));
+  auto cols = torch::empty({B, P}, optsF.dtype(torch::kInt64));
+  hipLaunchKernelGGL(scatter_kernel, dim3(P, nb), dim3(256), 0, stream,
                      (const unsigned long long*)best.data_ptr(),
                      y_orig.data_ptr<float>(), y_syn.data_ptr<float>(),
                      (long long*)rows.data_ptr<int64_t>(),
@@ -153,17 +185,23 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ncc_search_l2lab(
   return ncc_search_impl<true>(x_dec, y_dec, y_orig, ph, pw, use_mask);
 }
 
-// The bf16 LAB operands of the L2+LAB search, (3,H,W) fp32 -> (3,H,W) bf16:
-// what the tests' oracle needs (the device powf/cbrtf are not bit-identical
-// to the host's).
+// The bf16 LAB operands of the L2+LAB search, fp32 -> bf16 of the same shape,
+// (3,H,W) or (B,3,H,W): what the tests' oracle needs (the device powf/cbrtf
+// are not bit-identical to the host's).
 torch::Tensor ncc_lab_transform(torch::Tensor img) {
   CHECK_CUDA_CONTIG(img);
-  TORCH_CHECK(img.dim() == 3 && img.size(0) == 3, "img must be (3,H,W)");
+  const int64_t d = img.dim();
+  TORCH_CHECK((d == 3 || d == 4) && img.size(d - 3) == 3,
+              "img must be (3,H,W) or (B,3,H,W)");
   TORCH_CHECK(img.scalar_type() == torch::kFloat32, "img must be fp32");
+  const int64_t B = d == 4 ? img.size(0) : 1;
+  TORCH_CHECK(B <= NCC_GRID_YZ_MAX, "ncc_lab_transform: at most ",
+              NCC_GRID_YZ_MAX, " images in one call, got ", B);
   auto out = torch::empty_like(img, img.options().dtype(torch::kBFloat16));
-  const int64_t hw = img.size(1) * img.size(2);
-  if (hw > 0)
-    hipLaunchKernelGGL(lab_transform_kernel, grid1d(hw, 256), dim3(256), 0,
+  const int64_t hw = img.size(d - 2) * img.size(d - 1);
+  if (hw > 0 && B > 0)
+    hipLaunchKernelGGL(lab_transform_kernel,
+                       dim3(grid1d(hw, 256).x, (unsigned int)B), dim3(256), 0,
                        at::cuda::getCurrentCUDAStream(),
                        img.data_ptr<float>(), (bf16*)out.data_ptr(), hw);
   return out;

@@ -2,6 +2,7 @@
 
     python tools/bench_ncc.py [--iters 50] [--warmup 10] [--shape 320x960]
                               [--patch 20x24] [--torch-iters 3] [--cpu]
+                              [--batch 1]
 
 For one image of the given shape it prints one JSON line per run, in one
 process, interleaved over --rounds rounds:
@@ -9,6 +10,9 @@ process, interleaved over --rounds rounds:
   max time in ms of one ops.ncc_search call from device events (one pair per
   call, after a warm-up), and the rise of torch's peak allocated memory over
   one call;
+* with --batch B, in the same modes: pearson-batch / l2lab-batch, the same
+  timing and memory figures for one ops.ncc_search_batch call on B distinct
+  images (make_case with seeds 0..B-1); each line carries "batch": B;
 * torch-l2lab (unless --torch-iters 0): the same for
   ops.reference.ncc_search_ref(l2lab=True) run on the GPU tensors, which is
   what the GPU served this mode with before the L2 kernels, and the share
@@ -79,6 +83,7 @@ def main():
     ap.add_argument("--patch", default="20x24")
     ap.add_argument("--torch-iters", type=int, default=3)
     ap.add_argument("--cpu", action="store_true")
+    ap.add_argument("--batch", type=int, default=1)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_ncc: needs a GPU")
@@ -89,7 +94,10 @@ def main():
     imgs = [t.to(dev) for t in cpu_imgs]
     p = (h // ph) * (w // pw)
     head = dict(shape=[3, h, w], patch=[ph, pw], patches=p,
-                volume_bytes=p * (h - ph + 1) * (w - pw + 1) * 4)
+                volume_bytes=p * (h - ph + 1) * (w - pw + 1) * 4,
+                batch=args.batch)
+    cases = [make_case(h, w, seed=b) for b in range(args.batch)]
+    batch = [torch.stack([c[k] for c in cases]).to(dev) for k in range(3)]
 
     kernel = {}
     for rnd in range(args.rounds):
@@ -100,6 +108,12 @@ def main():
                                args.iters, args.warmup, dev)
                 kernel[(l2lab, mask)] = out
                 print(json.dumps(dict(head, run="l2lab" if l2lab else "pearson",
+                                      mask=mask, round=rnd, **t)), flush=True)
+                _, t = timed(lambda: ops.ncc_search_batch(*batch, ph, pw, mask,
+                                                          l2lab=l2lab),
+                             args.iters, args.warmup, dev)
+                print(json.dumps(dict(head, run=("l2lab" if l2lab else
+                                                 "pearson") + "-batch",
                                       mask=mask, round=rnd, **t)), flush=True)
     for mask in (True, False):
         if args.torch_iters:
