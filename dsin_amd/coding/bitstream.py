@@ -41,14 +41,41 @@ and a CPU.)
 
 Batches: ``compress_batch(model, x)`` takes ``x`` of shape (B,3,H,W) and
 returns a list of B byte strings, each a complete version-1 container of one
-image that ``decompress`` opens on its own; there is no multi-image
-container. ``decompress_batch(model, datas, y)`` takes such a list (from
+image that ``decompress`` opens on its own (the archive below holds several
+of them in one file). ``decompress_batch(model, datas, y)`` takes such a list (from
 ``compress_batch`` or from B ``compress`` calls) and returns batched
 ``x_dec`` / ``x_with_si``. The containers of one batch must agree in backend
 id, ``(C, Hb, Wb)`` and ``L``. With the hip and portable backends the B
 symbol volumes are entropy-coded together by the batched kernels
 (``encode_symbols_batch`` / ``decode_symbols_batch``): the images share one
 wave loop and each has a range coder of its own.
+
+Images of different sizes: ``compress_many(model, xs)`` takes a list of
+(3,H_b,W_b) images whose sizes may all differ and returns one ordinary
+version-1 single-image container per image, in input order;
+``decompress_many(model, datas, ys)`` takes such containers, which may
+differ in ``(Hb, Wb)`` but must agree in backend id, ``C`` and ``L``, and
+returns one ``(x_dec, x_with_si)`` pair per image. With the hip and portable
+backends all symbol volumes go through one ragged call
+(``encode_symbols_ragged`` / ``decode_symbols_ragged``): the images walk one
+wave counter and the smaller ones finish early. The networks run once per
+size group.
+
+Archive, the multi-image container (little-endian), written by
+``pack_archive(datas, names)`` and read by ``unpack_archive(data)``:
+
+    4s  magic  b"DSNA"
+    B   version (1)
+    I   count  number of entries
+    per entry:
+      I   container length in bytes
+      H   name length in bytes
+      ..  name, UTF-8 (may be empty)
+    ..  the containers back to back, in entry order
+
+Each container is a complete version-1 single-image stream. A bad magic or
+version, a truncated table, a truncated container and trailing bytes are
+ValueErrors.
 """
 
 from __future__ import annotations
@@ -60,13 +87,18 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from .entropy import (decode_symbols, decode_symbols_batch,
-                      encode_symbols_batch)
+                      decode_symbols_ragged, encode_symbols_batch,
+                      encode_symbols_ragged)
 
 MAGIC = b"DSIN"
 VERSION = 1
 BACKEND_IDS = {"torch": 0, "hip": 1, "portable": 2}
 _HEADER = struct.Struct("<4sBBHHHHII")
 HEADER_SIZE = _HEADER.size
+ARCHIVE_MAGIC = b"DSNA"
+ARCHIVE_VERSION = 1
+_ARCHIVE_HEADER = struct.Struct("<4sBI")
+_ARCHIVE_ENTRY = struct.Struct("<IH")
 
 
 def model_backend(model) -> str:
@@ -265,3 +297,159 @@ def decompress_batch(model, datas: Sequence[bytes],
                                    [p[4] for p in parsed], shape,
                                    device=centers.device, backend=backend)
     return _reconstruct(model, symbols, y)
+
+
+def _size_groups(keys) -> List[List[int]]:
+    """Indices grouped by equal key, groups in order of first appearance."""
+    groups = {}
+    for i, k in enumerate(keys):
+        groups.setdefault(k, []).append(i)
+    return list(groups.values())
+
+
+@torch.no_grad()
+def compress_many(model, xs: Sequence[torch.Tensor],
+                  backend: Optional[str] = None) -> List[bytes]:
+    """Encode images (3,H_b,W_b) whose sizes may differ to single-image
+    containers, in input order. One encoder pass per distinct size (the
+    images of a size stacked, sizes in order of first appearance) and one
+    encode_symbols_ragged call over all symbol volumes."""
+    if backend is not None and backend not in BACKEND_IDS:
+        raise ValueError(f"backend must be one of {tuple(BACKEND_IDS)}, got "
+                         f"{backend!r}")
+    from ..ops import conv as _conv
+    xs = list(xs)
+    if len(xs) < 1:
+        raise ValueError("compress_many: empty list")
+    for i, x in enumerate(xs):
+        if x.dim() != 3 or x.shape[0] != 3:
+            raise ValueError(f"compress_many: image {i} must be (3,H,W), got "
+                             f"{tuple(x.shape)}")
+    _conv.begin_step()
+    model.eval()
+    symbols: List[Optional[torch.Tensor]] = [None] * len(xs)
+    for group in _size_groups(tuple(x.shape) for x in xs):
+        sym = model.encoder(torch.stack([xs[i] for i in group])).symbols
+        for i, s in zip(group, sym):
+            symbols[i] = s
+    centers = model.encoder.quantizer.centers.detach()
+    if backend is None:
+        backend = model_backend(model)
+    payloads = encode_symbols_ragged(model.probclass, centers, symbols,
+                                     backend=backend)
+    crc = probclass_crc(model)
+    return [pack_container(backend, s.shape, centers.numel(), crc, p)
+            for s, p in zip(symbols, payloads)]
+
+
+@torch.no_grad()
+def decompress_many(model, datas: Sequence[bytes],
+                    ys: Optional[Sequence[torch.Tensor]] = None
+                    ) -> List[Tuple[torch.Tensor, Optional[torch.Tensor]]]:
+    """-> one (x_dec (1,3,H_b,W_b), x_with_si or None) per container; ys,
+    when given, holds one side image (3,H_b,W_b) per container. The
+    containers may differ in (Hb, Wb); backend id, C, L and CRC must agree
+    with the model and with each other. Every header problem, a ys of
+    another length and a side image of another size than its container are
+    ValueErrors raised before any network or kernel runs. One
+    decode_symbols_ragged call, then the networks once per size group."""
+    from ..ops import conv as _conv
+    datas = list(datas)
+    if len(datas) < 1:
+        raise ValueError("decompress_many: empty list")
+    parsed = [parse_container(d) for d in datas]
+    bid, _, L = parsed[0][:3]
+    backend = _check_header(model, *parsed[0][:4])
+    for i, (bid_i, shape_i, L_i, crc_i, _) in enumerate(parsed[1:], 1):
+        _check_header(model, bid_i, shape_i, L_i, crc_i)
+        if (bid_i, L_i) != (bid, L):
+            raise ValueError(
+                f"container {i}: backend id {bid_i}, L={L_i} differ from "
+                f"container 0 (backend id {bid}, L={L}); one call holds one "
+                f"kind of stream")
+    if ys is not None:
+        ys = list(ys)
+        if len(ys) != len(datas):
+            raise ValueError(f"decompress_many: {len(datas)} streams but "
+                             f"{len(ys)} side images")
+        for i, (y, p) in enumerate(zip(ys, parsed)):
+            want = (3, p[1][1] * 8, p[1][2] * 8)
+            if tuple(y.shape) != want:
+                raise ValueError(f"decompress_many: side image {i} must be "
+                                 f"{want}, got {tuple(y.shape)}")
+    centers = model.encoder.quantizer.centers.detach()
+    _conv.begin_step()
+    model.eval()
+    shapes = [p[1] for p in parsed]
+    symbols = decode_symbols_ragged(model.probclass, centers,
+                                    [p[4] for p in parsed], shapes,
+                                    device=centers.device, backend=backend)
+    out: List[Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]]] = \
+        [None] * len(datas)
+    for group in _size_groups(shapes):
+        y = None if ys is None else torch.stack([ys[i] for i in group])
+        x_dec, x_si = _reconstruct(
+            model, torch.stack([symbols[i] for i in group]), y)
+        for j, i in enumerate(group):
+            out[i] = (x_dec[j:j + 1],
+                      None if x_si is None else x_si[j:j + 1])
+    return out
+
+
+def pack_archive(datas: Sequence[bytes],
+                 names: Optional[Sequence[str]] = None) -> bytes:
+    """Containers (and optional names, one per container) -> one archive
+    (layout in the module docstring)."""
+    datas = [bytes(d) for d in datas]
+    names = [""] * len(datas) if names is None else list(names)
+    if len(names) != len(datas):
+        raise ValueError(f"archive: {len(datas)} containers but {len(names)} "
+                         f"names")
+    table = [_ARCHIVE_HEADER.pack(ARCHIVE_MAGIC, ARCHIVE_VERSION, len(datas))]
+    for d, name in zip(datas, names):
+        raw = name.encode("utf-8")
+        if len(raw) > 0xFFFF or len(d) > 0xFFFFFFFF:
+            raise ValueError(f"archive: entry {name!r} is too large")
+        table.append(_ARCHIVE_ENTRY.pack(len(d), len(raw)) + raw)
+    return b"".join(table + datas)
+
+
+def unpack_archive(data: bytes) -> Tuple[List[bytes], List[str]]:
+    """-> (containers, names). ValueError on a bad magic or version, a
+    truncated table, a truncated container or trailing bytes."""
+    if len(data) < _ARCHIVE_HEADER.size:
+        raise ValueError(f"archive: {len(data)} bytes is shorter than the "
+                         f"{_ARCHIVE_HEADER.size}-byte header")
+    magic, ver, count = _ARCHIVE_HEADER.unpack_from(data)
+    if magic != ARCHIVE_MAGIC:
+        raise ValueError(f"archive: bad magic {magic!r}")
+    if ver != ARCHIVE_VERSION:
+        raise ValueError(f"archive: version {ver}, this build reads "
+                         f"{ARCHIVE_VERSION}")
+    pos = _ARCHIVE_HEADER.size
+    sizes, names = [], []
+    for i in range(count):
+        if len(data) - pos < _ARCHIVE_ENTRY.size:
+            raise ValueError(f"archive: table truncated at entry {i} of "
+                             f"{count}")
+        n, m = _ARCHIVE_ENTRY.unpack_from(data, pos)
+        pos += _ARCHIVE_ENTRY.size
+        if len(data) - pos < m:
+            raise ValueError(f"archive: table truncated in the name of entry "
+                             f"{i}")
+        try:
+            names.append(data[pos:pos + m].decode("utf-8"))
+        except UnicodeDecodeError:
+            raise ValueError(f"archive: the name of entry {i} is not UTF-8")
+        pos += m
+        sizes.append(n)
+    datas = []
+    for i, n in enumerate(sizes):
+        if len(data) - pos < n:
+            raise ValueError(f"archive: container {i} truncated, the table "
+                             f"says {n} bytes, {len(data) - pos} present")
+        datas.append(bytes(data[pos:pos + n]))
+        pos += n
+    if pos != len(data):
+        raise ValueError(f"archive: {len(data) - pos} trailing bytes")
+    return datas, names

@@ -246,6 +246,147 @@ def decode_symbols_batch(pc: ProbClass, centers: torch.Tensor,
                                        backend=backend) for d in datas])
 
 
+def _ragged_setup(pc: ProbClass, centers: torch.Tensor, shapes, device,
+                  portable: bool):
+    """Checks + what the hip / portable ragged encoder and decoder share:
+    the wave-ordered positions and wave numbers of every distinct shape
+    (_wave_order runs once per shape), the descriptor rows (C, H, W, volume
+    offset, symbol offset) and the pad-filled flat value buffer."""
+    from .. import ops
+    ops.check_pc_shape(pc)
+    name = "portable" if portable else "hip"
+    if device.type != "cuda" and not portable:
+        raise ValueError("backend='hip' needs the model and symbols on a GPU")
+    pad = pc.context_size() // 2
+    Kh = pad + 1
+    Kc = Kh * pad + pad + 1
+    orders, desc, q_off, s_off = {}, [], 0, 0
+    for shape in shapes:
+        C, H, W = shape
+        if min(C, H, W) < 1:
+            raise ValueError(f"backend={name!r}: empty symbol volume {shape}")
+        if shape not in orders:
+            pos = np.concatenate(_wave_order(C, H, W, pad)).astype(np.int32)
+            orders[shape] = (pos, Kc * pos[:, 0] + Kh * pos[:, 1] + pos[:, 2])
+        desc.append((C, H, W, q_off, s_off))
+        q_off += (C + pad) * (H + 2 * pad) * (W + 2 * pad)
+        s_off += C * H * W
+    q = torch.full((q_off,), float(_pad_value(pc, centers)),
+                   dtype=torch.float32, device=device)
+    return ops, pad, orders, desc, q
+
+
+def _ragged_items(shapes, orders) -> np.ndarray:
+    """(n, 4) int32 items (b, c, h, w): image after image, each in its own
+    wave order, which is the encoder's order (b, t, c, h, w)."""
+    return np.concatenate([
+        np.concatenate([np.full((len(orders[s][0]), 1), b, np.int32),
+                        orders[s][0]], axis=1)
+        for b, s in enumerate(shapes)])
+
+
+def _encode_symbols_hip_ragged(pc, centers, symbols, portable) -> List[bytes]:
+    dev = centers.device
+    shapes = [tuple(int(v) for v in s.shape) for s in symbols]
+    ops, pad, orders, desc, q = _ragged_setup(pc, centers, shapes, dev,
+                                              portable)
+    cen = centers.float()
+    index = {s: torch.from_numpy(o[0]).to(dev).long()
+             for s, o in orders.items()}
+    syms, starts = [], [0]
+    for sym, shape, (C, H, W, q_off, _) in zip(symbols, shapes, desc):
+        sym = sym.to(dev)
+        vol = q[q_off:q_off + (C + pad) * (H + 2 * pad) * (W + 2 * pad)]
+        vol.view(C + pad, H + 2 * pad, W + 2 * pad)[
+            pad:, pad:H + pad, pad:W + pad] = cen[sym]
+        p = index[shape]
+        syms.append(sym[p[:, 0], p[:, 1], p[:, 2]])
+        starts.append(starts[-1] + p.shape[0])
+    items = torch.from_numpy(_ragged_items(shapes, orders)).to(dev)
+    return ops.pc_encode_ragged(pc, q, desc, items, starts, torch.cat(syms),
+                                portable=portable)
+
+
+def _decode_symbols_hip_ragged(pc, centers, datas, shapes, device,
+                               portable) -> List[torch.Tensor]:
+    ops, _, orders, desc, q = _ragged_setup(pc, centers, shapes, device,
+                                            portable)
+    B = len(shapes)
+    items = _ragged_items(shapes, orders)
+    t = np.concatenate([orders[s][1] for s in shapes]).astype(np.int64)
+    # images are in order and each is sorted by (t, c, h, w): a stable sort
+    # by t gives (t, b, c, h, w)
+    order = np.argsort(t, kind="stable")
+    items, t = items[order], t[order]
+    T = int(t[-1]) + 1
+    counts = np.bincount(t * B + items[:, 0], minlength=T * B)
+    seg = np.concatenate([[0], np.cumsum(counts)])
+    out = ops.pc_decode_ragged(pc, q, desc, torch.from_numpy(items).to(device),
+                               seg.tolist(), datas, centers,
+                               portable=portable)
+    return [out[so:so + C * H * W].view(C, H, W)
+            for C, H, W, _, so in desc]
+
+
+def _ragged_shapes(what: str, shapes) -> List[Tuple[int, int, int]]:
+    out = []
+    for s in shapes:
+        if len(s) != 3:
+            raise ValueError(f"{what}: every volume must be (C, H, W), got "
+                             f"{tuple(s)}")
+        out.append(tuple(int(v) for v in s))
+    if not out:
+        raise ValueError(f"{what}: empty batch")
+    return out
+
+
+@torch.no_grad()
+def encode_symbols_ragged(pc: ProbClass, centers: torch.Tensor,
+                          symbols: Sequence[torch.Tensor],
+                          backend: str = "torch") -> List[bytes]:
+    """symbols: B int64 volumes (C_b, H_b, W_b) whose shapes may all differ
+    -> B byte streams; element b is what encode_symbols gives for symbols[b]
+    with the same backend. "hip" and "portable" code the whole list in one
+    pass of the ragged kernels (ops.pc_encode_ragged, two launches); "torch"
+    loops over the images. An empty list or a volume that is not 3-D is a
+    ValueError."""
+    _check_backend(backend)
+    symbols = list(symbols)
+    _ragged_shapes("encode_symbols_ragged", [s.shape for s in symbols])
+    if backend in ("hip", "portable"):
+        return _encode_symbols_hip_ragged(pc, centers, symbols,
+                                          portable=backend == "portable")
+    return [encode_symbols(pc, centers, s, backend=backend) for s in symbols]
+
+
+@torch.no_grad()
+def decode_symbols_ragged(pc: ProbClass, centers: torch.Tensor,
+                          datas: Sequence[bytes],
+                          shapes: Sequence[Tuple[int, int, int]],
+                          device: Optional[torch.device] = None,
+                          backend: str = "torch") -> List[torch.Tensor]:
+    """Inverse of encode_symbols_ragged: stream b holds a (C, H, W) =
+    shapes[b] volume -> B int64 tensors. The streams may come from
+    encode_symbols_ragged, encode_symbols_batch or encode_symbols. "hip" and
+    "portable" decode all images in one wave loop over the merged schedule
+    (ops.pc_decode_ragged: the images walk one wave counter, the smaller
+    ones finish early); "torch" loops over the images. A short stream
+    decodes as decode_symbols decodes it. An empty list, a shape that is not
+    (C, H, W) or len(datas) != len(shapes) is a ValueError."""
+    _check_backend(backend)
+    datas = list(datas)
+    shapes = _ragged_shapes("decode_symbols_ragged", list(shapes))
+    if len(datas) != len(shapes):
+        raise ValueError(f"decode_symbols_ragged: {len(datas)} streams for "
+                         f"{len(shapes)} shapes")
+    device = torch.device(device or centers.device)
+    if backend in ("hip", "portable"):
+        return _decode_symbols_hip_ragged(pc, centers, datas, shapes, device,
+                                          portable=backend == "portable")
+    return [decode_symbols(pc, centers, d, s, device=device, backend=backend)
+            for d, s in zip(datas, shapes)]
+
+
 @torch.no_grad()
 def encode_symbols(pc: ProbClass, centers: torch.Tensor,
                    symbols: torch.Tensor, backend: str = "torch") -> bytes:

@@ -670,6 +670,151 @@ def pc_decode(pc, q_pad: torch.Tensor, pos: torch.Tensor, offsets,
                            portable)[0]
 
 
+# The ragged form: the images of a batch differ in (C, H, W). Their padded
+# volumes lie in one flat fp32 value buffer, their symbols in one flat int64
+# output; desc holds one row (C, H, W, volume offset, symbol offset) per
+# image and positions are items (b, c, h, w). Layouts: csrc/pc_batch_host.h.
+
+def _pc_ragged_args(name: str, pc, q: torch.Tensor, desc, items: torch.Tensor,
+                    portable: bool = False):
+    """Checks every ragged codec call makes; -> (the extension entry `name`,
+    which is looked up when it is called, k, L, fp32 contiguous q, flat descriptor list, int32 items on
+    its device, symbols in the batch)."""
+    k, L = check_pc_shape(pc)
+    if not q.is_cuda and not portable:
+        raise ValueError("pc codec: the hip backend needs GPU tensors")
+    if q.dim() != 1:
+        raise ValueError(f"pc codec: a ragged value buffer must be flat, got "
+                         f"{tuple(q.shape)}")
+    rows = [tuple(int(v) for v in r) for r in
+            (desc.tolist() if isinstance(desc, torch.Tensor) else desc)]
+    if not rows or any(len(r) != 5 for r in rows):
+        raise ValueError("pc codec: the descriptor table must hold at least "
+                         "one row (C, H, W, volume offset, symbol offset)")
+    if len(rows) > PC_MAX_BATCH:
+        raise ValueError(f"pc codec: a batch of {len(rows)} images is above "
+                         f"the {PC_MAX_BATCH} one call codes; split it")
+    total = 0
+    for b, (C, H, W, qo, so) in enumerate(rows):
+        if not (1 <= C <= 0xFFFF and 1 <= H <= 0xFFFF and 1 <= W <= 0xFFFF):
+            raise ValueError(f"pc codec: image {b}: C, H, W must be in "
+                             f"[1, 65535], got {(C, H, W)}")
+        total += C * H * W
+    for what, spans, size in (
+            ("padded volumes", [(r[3], (r[0] + 4) * (r[1] + 8) * (r[2] + 8))
+                                for r in rows], q.numel()),
+            ("symbol ranges", [(r[4], r[0] * r[1] * r[2]) for r in rows],
+             total)):
+        end = 0
+        for off, n in sorted(spans):
+            if off < end or off + n > size:
+                raise ValueError(f"pc codec: the {what} of the descriptor "
+                                 f"table must lie inside their buffer of "
+                                 f"{size} values without overlap")
+            end = off + n
+    if items.dim() != 2 or items.shape[1] != 4:
+        raise ValueError("pc codec: items must be (n, 4) = (b, c, h, w)")
+    where = ("on a GPU tensor" if q.is_cuda else
+             "for the portable codec on CPU tensors")
+
+    def fn(*args):  # looked up at the call, after the caller's own checks
+        return _require_ext(name, where)(*args)
+    return (fn, k, L, q.float().contiguous(),
+            [v for r in rows for v in r],
+            items.to(device=q.device, dtype=torch.int32).contiguous(), total)
+
+
+def _pc_offsets(name: str, what: str, offs, count: int, total: int
+                ) -> List[int]:
+    """count + 1 offsets running from 0 to total without decreasing."""
+    offs = [int(o) for o in offs]
+    if (len(offs) != count + 1 or offs[0] != 0 or offs[-1] != total
+            or any(b < a for a, b in zip(offs, offs[1:]))):
+        raise ValueError(f"{name}: {what} must be {count + 1} values running "
+                         f"from 0 to {total} without decreasing")
+    return offs
+
+
+@torch.no_grad()
+def pc_freqs_ragged(pc, q: torch.Tensor, desc, items: torch.Tensor,
+                    packed: Optional[torch.Tensor] = None,
+                    portable: bool = False
+                    ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Context model at items (n, 4) = (b, c, h, w) of a ragged batch ->
+    (fp32 logits (n, L), int32 frequency tables (n, L)), row i for item i,
+    one launch on the GPU. Row i is what pc_freqs gives for that position of
+    image b alone, bit for bit."""
+    fn, k, L, q, desc, items, _ = _pc_ragged_args("pc_freqs_ragged", pc, q,
+                                                  desc, items, portable)
+    if packed is None:
+        packed = pc_pack_weights(pc)
+    return fn(q, desc, items, packed.to(q.device), k, L, portable)
+
+
+@torch.no_grad()
+def pc_encode_ragged(pc, q: torch.Tensor, desc, items: torch.Tensor, starts,
+                     symbols: torch.Tensor, portable: bool = False
+                     ) -> List[bytes]:
+    """Range-code a ragged batch: items (n, 4) sorted by (b, t, c, h, w),
+    image b owns items and symbols [starts[b], starts[b+1]), symbols (n,) in
+    item order. One stream per image, the bytes pc_encode gives for that
+    image alone. GPU: one pc_freqs_ragged launch over all items, one
+    rc_encode launch with a workgroup per image, one device-to-host copy."""
+    fn, k, L, q, desc, items, _ = _pc_ragged_args("pc_encode_ragged", pc, q,
+                                                  desc, items, portable)
+    B, n = len(desc) // 5, items.shape[0]
+    starts = _pc_offsets("pc_encode_ragged", "starts", starts, B, n)
+    if symbols.dim() != 1 or symbols.shape[0] != n:
+        raise ValueError(f"pc_encode_ragged: symbols must be ({n},), one per "
+                         f"item, got {tuple(symbols.shape)}")
+    syms = symbols.to(device=q.device, dtype=torch.int32).contiguous()
+    flat = fn(q, desc, items, starts, syms, pc_pack_weights(pc).to(q.device),
+              k, L, portable).cpu().numpy()
+    out = []
+    for b in range(B):
+        row, cap = 24 * b + 3 * starts[b], 3 * (starts[b + 1] - starts[b]) + 16
+        m = int.from_bytes(flat[row:row + 8].tobytes(), "little")
+        if m > cap:
+            raise RuntimeError(f"pc_encode_ragged: stream {b} of {m} bytes "
+                               f"overran its {cap}-byte buffer")
+        out.append(flat[row + 8:row + 8 + m].tobytes())
+    return out
+
+
+@torch.no_grad()
+def pc_decode_ragged(pc, q: torch.Tensor, desc, items: torch.Tensor, seg,
+                     datas: Sequence[bytes], centers: torch.Tensor,
+                     portable: bool = False) -> torch.Tensor:
+    """Wavefront decode of a ragged batch into the flat value buffer q,
+    filled in place with centers[symbol]. items (n, 4) are sorted by (t, b,
+    c, h, w) with t = 25c + 5h + w; seg holds T*B + 1 cumulative offsets:
+    image b's share of wave t is items[seg[t*B+b]:seg[t*B+b+1]]. Returns the
+    flat int64 symbols, image b's C*H*W values at its descriptor's symbol
+    offset. One state init plus two launches per non-empty wave of the merged
+    schedule, issued from C++ without a host sync; an image with nothing in
+    a wave leaves its coder untouched."""
+    fn, k, L, q_c, desc, items, _ = _pc_ragged_args("pc_decode_ragged", pc, q,
+                                                    desc, items, portable)
+    if q_c.data_ptr() != q.data_ptr():
+        raise ValueError("pc_decode_ragged: q must be fp32 and contiguous")
+    B, n = len(desc) // 5, items.shape[0]
+    if len(datas) != B:
+        raise ValueError(f"pc_decode_ragged: {len(datas)} streams for a batch "
+                         f"of {B}")
+    seg = [int(s) for s in seg]
+    if len(seg) < B + 1 or (len(seg) - 1) % B:
+        raise ValueError(f"pc_decode_ragged: the segment table must hold "
+                         f"T*{B} + 1 values, got {len(seg)}")
+    seg = _pc_offsets("pc_decode_ragged", "the segment table", seg,
+                      len(seg) - 1, n)
+    data_offs = [0]
+    for d in datas:
+        data_offs.append(data_offs[-1] + len(d))
+    return fn(q, desc, items, seg, pc_pack_weights(pc).to(q.device), k, L,
+              _pc_bytes_tensor(b"".join(datas), q.device), data_offs,
+              centers.detach().to(q.device).float().contiguous(), portable)
+
+
 # re-exports used across the package
 kitti_normalize = ref.kitti_normalize
 kitti_denormalize = ref.kitti_denormalize

@@ -103,6 +103,20 @@ torch::Tensor pc_decode(torch::Tensor q_pad, torch::Tensor pos,
                         int64_t k, int64_t L, torch::Tensor data,
                         std::vector<int64_t> data_offs, torch::Tensor centers,
                         bool portable);
+std::tuple<torch::Tensor, torch::Tensor> pc_freqs_ragged(
+    torch::Tensor q, std::vector<int64_t> desc, torch::Tensor items,
+    torch::Tensor wts, int64_t k, int64_t L, bool portable);
+torch::Tensor pc_encode_ragged(torch::Tensor q, std::vector<int64_t> desc,
+                               torch::Tensor items,
+                               std::vector<int64_t> starts, torch::Tensor syms,
+                               torch::Tensor wts, int64_t k, int64_t L,
+                               bool portable);
+torch::Tensor pc_decode_ragged(torch::Tensor q, std::vector<int64_t> desc,
+                               torch::Tensor items, std::vector<int64_t> seg,
+                               torch::Tensor wts, int64_t k, int64_t L,
+                               torch::Tensor data,
+                               std::vector<int64_t> data_offs,
+                               torch::Tensor centers, bool portable);
 torch::Tensor rc_encode(torch::Tensor syms, torch::Tensor freqs);
 torch::Tensor rc_decode(torch::Tensor data, torch::Tensor freqs);
 torch::Tensor rc_encode_host(torch::Tensor syms, torch::Tensor freqs);
@@ -204,6 +218,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q_pad"), py::arg("pos"), py::arg("offsets"), py::arg("wts"),
         py::arg("k"), py::arg("L"), py::arg("data"), py::arg("data_offs"),
         py::arg("centers"), py::arg("portable") = false);
+  // Ragged form: images of different (C, H, W) in one flat value buffer q
+  // (which picks the device), a descriptor table of 5 values per image
+  // (C, H, W, volume offset, symbol offset) and items (n, 4) = (b, c, h, w).
+  m.def("pc_freqs_ragged", &dsin::pc_freqs_ragged,
+        "context model per item: compact (n, L) logits and tables",
+        py::arg("q"), py::arg("desc"), py::arg("items"), py::arg("wts"),
+        py::arg("k"), py::arg("L"), py::arg("portable") = false);
+  m.def("pc_encode_ragged", &dsin::pc_encode_ragged,
+        "context model + range encoder: flat length-prefixed rows",
+        py::arg("q"), py::arg("desc"), py::arg("items"), py::arg("starts"),
+        py::arg("syms"), py::arg("wts"), py::arg("k"), py::arg("L"),
+        py::arg("portable") = false);
+  m.def("pc_decode_ragged", &dsin::pc_decode_ragged,
+        "wavefront decoder over the merged schedule of a ragged batch",
+        py::arg("q"), py::arg("desc"), py::arg("items"), py::arg("seg"),
+        py::arg("wts"), py::arg("k"), py::arg("L"), py::arg("data"),
+        py::arg("data_offs"), py::arg("centers"),
+        py::arg("portable") = false);
   m.def("rc_encode", &dsin::rc_encode,
         "device range encoder, one workgroup per image");
   m.def("rc_decode", &dsin::rc_decode, "device range decoder, given tables");

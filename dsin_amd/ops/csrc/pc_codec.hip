@@ -9,6 +9,14 @@
 // pc_decode) dispatch on the device of q_pad: kernels for a GPU tensor, the
 // host build of the portable backend for a CPU tensor.
 //
+// Next to this uniform form stands a ragged one for images of different
+// shapes (pc_freqs_ragged, pc_encode_ragged, pc_decode_ragged): one flat
+// value buffer, a per-image descriptor table and items (b, c, h, w); the
+// layouts are in pc_batch_host.h. Each stage has one __device__ body
+// (pc_freqs_body, rc_encode_body, rc_decode_wave_body) holding everything
+// after "where is my image, where is my position, where do my rows go", and
+// two __global__ kernels that answer those questions and call it.
+//
 // pc_freqs: one workgroup per (queried position (c, h, w), image); the image
 // is blockIdx.y. The position's 5x9x9 causal context is read from the padded
 // value buffer q_pad (C+4, H+8, W+8) of its image and pushed through the
@@ -124,12 +132,17 @@ __device__ __forceinline__ void pc_layer(const float* in, float* out,
   }
 }
 
+// What every pc_freqs workgroup does once it knows its image (q_pad, the
+// (C+4, H+8, W+8) volume), its position (c, h, w) and its output rows
+// (logits, freqs: L values each): stage the context, run the conv chain,
+// write logits and table. A position outside the volume, or live == false
+// (the ragged kernel: an item that names no image), writes the table of ones
+// and reads nothing.
 template <bool PORTABLE>
-__global__ void __launch_bounds__(PC_THREADS)
-pc_freqs_kernel(const float* __restrict__ q_pad, int64_t q_stride, int C,
-                int H, int W, const int* __restrict__ pos,
-                const float* __restrict__ wts, int k, int kp, int L,
-                float* __restrict__ logits, int* __restrict__ freqs) {
+__device__ __forceinline__ void pc_freqs_body(
+    const float* __restrict__ q_pad, int C, int H, int W, bool live, int c,
+    int h, int w, const float* __restrict__ wts, int k, int kp, int L,
+    float* __restrict__ logits, int* __restrict__ freqs) {
   __shared__ float s_in[pc::SIN + 3];
   __shared__ float s_a0[pc::MAX_K * pc::S0];
   __shared__ float s_a1[pc::MAX_K * pc::S1];
@@ -138,16 +151,11 @@ pc_freqs_kernel(const float* __restrict__ q_pad, int64_t q_stride, int C,
   __shared__ float s_lg[pc::MAX_L];
   __shared__ uint32_t s_u[pc::MAX_L];  // PORTABLE table weights
 
-  // position blockIdx.x of image blockIdx.y; outputs are (B, n, L)
-  const int64_t ip = blockIdx.x;
-  const int64_t b = (int64_t)blockIdx.y * gridDim.x + ip;
   const int tid = threadIdx.x;
-  const int c = pos[3 * ip], h = pos[3 * ip + 1], w = pos[3 * ip + 2];
-  q_pad += (int64_t)blockIdx.y * q_stride;
-  if (c < 0 || c >= C || h < 0 || h >= H || w < 0 || w >= W) {
+  if (!live || c < 0 || c >= C || h < 0 || h >= H || w < 0 || w >= W) {
     if (tid < L) {  // never reached through the Python wrappers
-      logits[b * L + tid] = 0.f;
-      freqs[b * L + tid] = 1;
+      logits[tid] = 0.f;
+      freqs[tid] = 1;
     }
     return;
   }
@@ -201,8 +209,8 @@ pc_freqs_kernel(const float* __restrict__ q_pad, int64_t q_stride, int C,
     __syncthreads();
     if (tid < L) {
       const uint64_t S = pc::table_sum(s_u, L, finite);
-      logits[b * L + tid] = s_lg[tid];
-      freqs[b * L + tid] = pc::table_entry(s_u[tid], S, L);
+      logits[tid] = s_lg[tid];
+      freqs[tid] = pc::table_entry(s_u[tid], S, L);
     }
   } else if (tid < L) {
     float m = s_lg[0];
@@ -211,9 +219,58 @@ pc_freqs_kernel(const float* __restrict__ q_pad, int64_t q_stride, int C,
     for (int l = 0; l < L; ++l) sum += expf(s_lg[l] - m);
     const float p = expf(s_lg[tid] - m) / sum;
     int f = (int)floorf(p * (float)(65536 - L));
-    logits[b * L + tid] = s_lg[tid];
-    freqs[b * L + tid] = f < 1 ? 1 : f;
+    logits[tid] = s_lg[tid];
+    freqs[tid] = f < 1 ? 1 : f;
   }
+}
+
+// Uniform form: position blockIdx.x of image blockIdx.y; outputs (B, n, L).
+template <bool PORTABLE>
+__global__ void __launch_bounds__(PC_THREADS)
+pc_freqs_kernel(const float* __restrict__ q_pad, int64_t q_stride, int C,
+                int H, int W, const int* __restrict__ pos,
+                const float* __restrict__ wts, int k, int kp, int L,
+                float* __restrict__ logits, int* __restrict__ freqs) {
+  const int64_t ip = blockIdx.x;
+  const int64_t b = (int64_t)blockIdx.y * gridDim.x + ip;
+  pc_freqs_body<PORTABLE>(q_pad + (int64_t)blockIdx.y * q_stride, C, H, W,
+                          true, pos[3 * ip], pos[3 * ip + 1], pos[3 * ip + 2],
+                          wts, k, kp, L, logits + b * L, freqs + b * L);
+}
+
+// Per-image descriptor of the ragged form (pcb::DESC int64 words per image,
+// layout in pc_batch_host.h): C, H, W, offset of the padded volume in the
+// flat value buffer, offset of the symbols in the flat output.
+struct PcImage {
+  int C, H, W;
+  int64_t q_off, sym_off;
+};
+
+__device__ __forceinline__ PcImage pc_image(const int64_t* __restrict__ desc,
+                                            int64_t b) {
+  const int64_t* d = desc + pcb::DESC * b;
+  return PcImage{(int)d[0], (int)d[1], (int)d[2], d[3], d[4]};
+}
+
+// Ragged form: one workgroup per item (b, c, h, w) of items (n, 4); row
+// blockIdx.x of compact (n, L) outputs. The images differ in size and lie
+// in one flat value buffer q.
+template <bool PORTABLE>
+__global__ void __launch_bounds__(PC_THREADS)
+pc_freqs_ragged_kernel(const float* __restrict__ q,
+                       const int64_t* __restrict__ desc, int B,
+                       const int* __restrict__ items,
+                       const float* __restrict__ wts, int k, int kp, int L,
+                       float* __restrict__ logits, int* __restrict__ freqs) {
+  const int64_t row = blockIdx.x;
+  const int* it = items + 4 * row;
+  const int b = it[0];
+  const bool live = b >= 0 && b < B;
+  PcImage im{0, 0, 0, 0, 0};
+  if (live) im = pc_image(desc, b);
+  pc_freqs_body<PORTABLE>(q + im.q_off, im.C, im.H, im.W, live, it[1], it[2],
+                          it[3], wts, k, kp, L, logits + row * L,
+                          freqs + row * L);
 }
 
 // ---------------------------------------------------------------------------
@@ -226,17 +283,14 @@ pc_freqs_kernel(const float* __restrict__ q_pad, int64_t q_stride, int C,
 constexpr int RC_CHUNK = 256;
 constexpr int RC_WIN = RC_CHUNK * rc::MAX_SHIFTS;  // bytes a chunk can read
 
-// One workgroup per image: syms (B, n), freqs (B, n, L), out (B, 8 + cap).
-// Row b of out: 8 bytes little-endian payload length, then the payload (cap
-// bytes).
-__global__ void __launch_bounds__(RC_CHUNK)
-rc_encode_kernel(const int* __restrict__ syms, const int* __restrict__ freqs,
-                 int64_t n, int L, uint8_t* __restrict__ out, uint64_t cap) {
+// What an encoder workgroup does once it knows its image: n symbols syms
+// against tables freqs (n, L) into the row out: 8 bytes little-endian
+// payload length, then the payload (cap bytes).
+__device__ __forceinline__ void rc_encode_body(
+    const int* __restrict__ syms, const int* __restrict__ freqs, int64_t n,
+    int L, uint8_t* __restrict__ out, uint64_t cap) {
   __shared__ uint32_t s_cum[RC_CHUNK], s_f[RC_CHUNK], s_tot[RC_CHUNK];
   const int tid = threadIdx.x;
-  syms += (int64_t)blockIdx.x * n;
-  freqs += (int64_t)blockIdx.x * n * L;
-  out += (int64_t)blockIdx.x * (8 + cap);
   rc::State st;
   rc::init(st);
   const rc::ByteSink sink{out + 8, cap};
@@ -267,6 +321,29 @@ rc_encode_kernel(const int* __restrict__ syms, const int* __restrict__ freqs,
     rc::finish(st, sink);
     for (int i = 0; i < 8; ++i) out[i] = (uint8_t)((st.pos >> (8 * i)) & 0xFF);
   }
+}
+
+// Uniform form, one workgroup per image: syms (B, n), freqs (B, n, L), out
+// (B, 8 + cap).
+__global__ void __launch_bounds__(RC_CHUNK)
+rc_encode_kernel(const int* __restrict__ syms, const int* __restrict__ freqs,
+                 int64_t n, int L, uint8_t* __restrict__ out, uint64_t cap) {
+  rc_encode_body(syms + (int64_t)blockIdx.x * n,
+                 freqs + (int64_t)blockIdx.x * n * L, n, L,
+                 out + (int64_t)blockIdx.x * (8 + cap), cap);
+}
+
+// Ragged form, one workgroup per image b over symbols [starts[b],
+// starts[b+1]) of the flat syms (n) and freqs (n, L); its row starts at
+// pcb::ragged_row_offset of the flat out and holds 3 n_b + 16 payload bytes.
+__global__ void __launch_bounds__(RC_CHUNK)
+rc_encode_ragged_kernel(const int* __restrict__ syms,
+                        const int* __restrict__ freqs,
+                        const int64_t* __restrict__ starts, int L,
+                        uint8_t* __restrict__ out) {
+  const int64_t b = blockIdx.x, s = starts[b], n = starts[b + 1] - s;
+  rc_encode_body(syms + s, freqs + s * L, n, L,
+                 out + pcb::ragged_row_offset(b, s), (uint64_t)(3 * n + 16));
 }
 
 // The payload of image b: data[offs[b], offs[b+1]) of the concatenated
@@ -303,35 +380,26 @@ struct WindowSource {
   }
 };
 
-// One workgroup per image b = blockIdx.x: decodes nw symbols against
-// freqs[b] of (B, nw, L), advancing state[b]. The image's bytes are its own
-// slice of data (rc_image_bytes), so the window and every later read are
-// bounded by that image's payload: past its end the coder reads 0, never the
-// next image's first bytes. With pos set, symbol i goes to out[b, c, h, w]
-// and centers[s] into q_pad[b] at that position; with pos == nullptr it goes
-// to out[b, i] (out_stride = nw).
-__global__ void __launch_bounds__(RC_CHUNK)
-rc_decode_wave_kernel(rc::State* state, const uint8_t* __restrict__ data_all,
-                      uint64_t len_all, const int64_t* __restrict__ offs,
-                      const int* __restrict__ freqs,
-                      const int* __restrict__ pos, int64_t nw, int L,
-                      const float* __restrict__ centers,
-                      float* __restrict__ q_pad, int64_t q_stride, int C,
-                      int H, int W, int64_t* __restrict__ out,
-                      int64_t out_stride) {
+// What a decoder workgroup does once it knows its image: decodes nw symbols
+// against the rows of freqs (nw, L), advancing *state. bytes is the image's
+// own payload, so the window and every later read are bounded by it: past
+// its end the coder reads 0, never the next image's first bytes. With pos
+// set, symbol i belongs to (c, h, w) = pos[i * pos_stride + 0..2] of the
+// image's (C, H, W) volume: it goes to out[c, h, w] and centers[s] into
+// q_pad at that position; with pos == nullptr it goes to out[i].
+__device__ __forceinline__ void rc_decode_wave_body(
+    rc::State* state, const rc::ByteSource bytes,
+    const int* __restrict__ freqs, const int* __restrict__ pos,
+    int pos_stride, int64_t nw, int L, const float* __restrict__ centers,
+    float* __restrict__ q_pad, int C, int H, int W,
+    int64_t* __restrict__ out) {
   __shared__ uint32_t s_cum[RC_CHUNK * (rc::MAX_L + 1)];
   __shared__ uint8_t s_win[RC_WIN];
   __shared__ int s_sym[RC_CHUNK];
   __shared__ rc::State s_state;
   const int tid = threadIdx.x;
-  const int64_t img = blockIdx.x;
-  const rc::ByteSource bytes = rc_image_bytes(data_all, len_all, offs, img);
   const uint8_t* data = bytes.buf;
   const uint64_t len = bytes.len;
-  state += img;
-  freqs += img * nw * L;
-  out += img * out_stride;
-  if (pos != nullptr) q_pad += img * q_stride;
   if (tid == 0) s_state = *state;
   __syncthreads();
   for (int64_t base = 0; base < nw; base += RC_CHUNK) {
@@ -356,7 +424,8 @@ rc_decode_wave_kernel(rc::State* state, const uint8_t* __restrict__ data_all,
       if (pos == nullptr) {
         out[i] = s;
       } else {
-        const int c = pos[3 * i], h = pos[3 * i + 1], w = pos[3 * i + 2];
+        const int* p = pos + i * pos_stride;
+        const int c = p[0], h = p[1], w = p[2];
         if (c >= 0 && c < C && h >= 0 && h < H && w >= 0 && w < W) {
           out[((int64_t)c * H + h) * W + w] = s;
           q_pad[((int64_t)(c + 4) * (H + 8) + (h + 4)) * (W + 8) + (w + 4)] =
@@ -367,6 +436,55 @@ rc_decode_wave_kernel(rc::State* state, const uint8_t* __restrict__ data_all,
     __syncthreads();
   }
   if (tid == 0) *state = s_state;
+}
+
+// Uniform form, one workgroup per image b = blockIdx.x: freqs (B, nw, L),
+// pos (nw, 3) shared by the images, q_pad (B, C+4, H+8, W+8), out row b of
+// out_stride values (C*H*W, or nw when pos == nullptr).
+__global__ void __launch_bounds__(RC_CHUNK)
+rc_decode_wave_kernel(rc::State* state, const uint8_t* __restrict__ data_all,
+                      uint64_t len_all, const int64_t* __restrict__ offs,
+                      const int* __restrict__ freqs,
+                      const int* __restrict__ pos, int64_t nw, int L,
+                      const float* __restrict__ centers,
+                      float* __restrict__ q_pad, int64_t q_stride, int C,
+                      int H, int W, int64_t* __restrict__ out,
+                      int64_t out_stride) {
+  const int64_t img = blockIdx.x;
+  if (pos != nullptr) q_pad += img * q_stride;
+  rc_decode_wave_body(state + img,
+                      rc_image_bytes(data_all, len_all, offs, img),
+                      freqs + img * nw * L, pos, 3, nw, L, centers, q_pad, C,
+                      H, W, out + img * out_stride);
+}
+
+// Ragged form, one workgroup per image b = blockIdx.x, for wave t of the
+// merged schedule: seg is the (T*B + 1) segment table over items (n, 4)
+// sorted by (t, b, c, h, w), freqs the compact tables of the wave (row 0 is
+// item seg[t*B]). The workgroup decodes items [seg[t*B+b], seg[t*B+b+1]) into
+// its image's volume of the flat value buffer q and its range of the flat
+// out. An empty segment returns at once: the state stays untouched and no
+// byte is read.
+__global__ void __launch_bounds__(RC_CHUNK)
+rc_decode_wave_ragged_kernel(rc::State* state,
+                             const uint8_t* __restrict__ data_all,
+                             uint64_t len_all,
+                             const int64_t* __restrict__ offs,
+                             const int* __restrict__ freqs,
+                             const int* __restrict__ items,
+                             const int64_t* __restrict__ seg, int64_t t,
+                             const int64_t* __restrict__ desc, int L,
+                             const float* __restrict__ centers,
+                             float* __restrict__ q,
+                             int64_t* __restrict__ out) {
+  const int64_t b = blockIdx.x, B = gridDim.x;
+  const int64_t w0 = seg[t * B], lo = seg[t * B + b], hi = seg[t * B + b + 1];
+  if (hi <= lo) return;
+  const PcImage im = pc_image(desc, b);
+  rc_decode_wave_body(state + b, rc_image_bytes(data_all, len_all, offs, b),
+                      freqs + (lo - w0) * L, items + 4 * lo + 1, 4, hi - lo, L,
+                      centers, q + im.q_off, im.C, im.H, im.W,
+                      out + im.sym_off);
 }
 
 // ---------------------------------------------------------------------------
@@ -463,6 +581,57 @@ static void pc_host_eval(const PcHostArgs& a, int64_t B, int64_t q_stride,
       else
         pc_host_range_libm(ab, plo, phi);
     });
+  });
+}
+
+// Ragged form: items (b, c, h, w) of images that differ in size. a.pos is
+// the (n, 4) item list, a.q_pad the flat value buffer; Hp and Wp come from
+// the item's descriptor. Rows of logits and freqs are compact (n, L).
+template <class Fma>
+static __forceinline__ void pc_host_items_impl(const PcHostArgs& a,
+                                               const int64_t* desc,
+                                               int64_t lo, int64_t hi) {
+  pc::Scratch scratch;
+  float lg[pc::MAX_L];
+  const int L = a.wts.L;
+  for (int64_t i = lo; i < hi; ++i) {
+    const int* it = a.pos + 4 * i;
+    const pcb::Image im = pcb::image_of(desc, it[0]);
+    pc::eval_position<Fma>(a.q_pad + im.q_off, im.H + 8, im.W + 8, it[1],
+                           it[2], it[3], a.wts, scratch, lg, a.freqs + i * L);
+    if (a.logits)
+      for (int l = 0; l < L; ++l) a.logits[i * L + l] = lg[l];
+  }
+}
+
+static void pc_host_items_libm(const PcHostArgs& a, const int64_t* desc,
+                               int64_t lo, int64_t hi) {
+  pc_host_items_impl<pc::FmaLibm>(a, desc, lo, hi);
+}
+
+#if PC_HOST_HAS_HW_PATH
+__attribute__((target("avx2,fma"))) static void pc_host_items_hw(
+    const PcHostArgs& a, const int64_t* desc, int64_t lo, int64_t hi) {
+  pc_host_items_impl<pc::FmaBuiltin>(a, desc, lo, hi);
+}
+#else
+static void pc_host_items_hw(const PcHostArgs& a, const int64_t* desc,
+                             int64_t lo, int64_t hi) {
+  pc_host_items_libm(a, desc, lo, hi);
+}
+#endif
+
+// Tables (and logits) of items [lo, hi), spread over the threads item by
+// item, so a wave fills them whichever images it comes from.
+static void pc_host_eval_ragged(const PcHostArgs& a, const int64_t* desc,
+                                int64_t lo, int64_t hi) {
+  if (hi <= lo) return;
+  const bool hw = pc_host_cpu_has_fma() && !g_pc_host_force_libm.load();
+  host_parallel_for(lo, hi, 1, [&](int64_t s, int64_t e) {
+    if (hw)
+      pc_host_items_hw(a, desc, s, e);
+    else
+      pc_host_items_libm(a, desc, s, e);
   });
 }
 
@@ -754,6 +923,256 @@ torch::Tensor pc_decode(torch::Tensor q_pad, torch::Tensor pos,
                        centers.data_ptr<float>(), q_pad.data_ptr<float>(),
                        q_pad.stride(0), C, H, W, out.data_ptr<int64_t>(),
                        (int64_t)C * H * W);
+  }
+  return out;
+}
+
+// ---------------------------------------------------------------------------
+// Ragged entry points: the images of a batch differ in (C, H, W). q is the
+// flat fp32 value buffer and decides the device; desc is the descriptor
+// table (B rows of pcb::DESC values, layout in pc_batch_host.h) and items
+// the int32 (n, 4) list of (b, c, h, w). Everything is validated on the
+// host before the first launch.
+// ---------------------------------------------------------------------------
+
+// -> B. The symbol ranges of desc must tile an output of sum(C_b*H_b*W_b)
+// values.
+static int64_t pc_ragged_check(const torch::Tensor& q,
+                               const std::vector<int64_t>& desc,
+                               const torch::Tensor& items,
+                               const torch::Tensor& wts, int64_t k, int64_t L,
+                               bool on_gpu, bool portable,
+                               int64_t* sym_total) {
+  TORCH_CHECK(on_gpu || portable,
+              "pc_codec: CPU tensors are served by the portable backend only");
+  pc_check_tensor(q, "the value buffer", on_gpu);
+  pc_check_tensor(items, "items", on_gpu);
+  pc_check_tensor(wts, "packed weights", on_gpu);
+  TORCH_CHECK(k >= 1 && k <= pc::MAX_K, "pc_codec: k must be in [1, ",
+              pc::MAX_K, "]");
+  TORCH_CHECK(L >= 1 && L <= pc::MAX_L, "pc_codec: L must be in [1, ",
+              pc::MAX_L, "]");
+  TORCH_CHECK(q.scalar_type() == torch::kFloat32 && q.dim() == 1,
+              "pc_codec: the ragged value buffer must be fp32 (numel,)");
+  TORCH_CHECK(items.scalar_type() == torch::kInt32 && items.dim() == 2 &&
+                  items.size(1) == 4,
+              "pc_codec: items must be int32 (n, 4)");
+  TORCH_CHECK(wts.scalar_type() == torch::kFloat32 &&
+                  wts.numel() == (int64_t)pc::packed_numel((int)k, (int)L),
+              "pc_codec: packed weights have the wrong size");
+  TORCH_CHECK(!desc.empty() && desc.size() % pcb::DESC == 0,
+              "pc_codec: the descriptor table must hold 5 values per image");
+  const int64_t B = (int64_t)desc.size() / pcb::DESC;
+  TORCH_CHECK(B <= PC_MAX_B, "pc_codec: batch size must be in [1, ", PC_MAX_B,
+              "]");
+  int64_t total = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t* d = desc.data() + pcb::DESC * b;
+    TORCH_CHECK(d[0] >= 1 && d[0] <= 65535 && d[1] >= 1 && d[1] <= 65535 &&
+                    d[2] >= 1 && d[2] <= 65535,
+                "pc_codec: image ", b, ": C, H, W must be in [1, 65535]");
+    total += d[0] * d[1] * d[2];
+    TORCH_CHECK(total <= ((int64_t)1 << 40), "pc_codec: the batch holds more "
+                "than 2^40 symbols");
+  }
+  const char* bad = pcb::desc_problem(desc.data(), B, q.numel(), total);
+  TORCH_CHECK(bad == nullptr, "pc_codec: descriptor table: ", bad);
+  *sym_total = total;
+  if (on_gpu) return B;  // the kernels test every item themselves
+  const int64_t i = pcb::first_bad_item(items.data_ptr<int>(), items.size(0),
+                                        desc.data(), B);
+  TORCH_CHECK(i == items.size(0), "pc_codec host: item ", i,
+              " names no image or lies outside its image's volume");
+  return B;
+}
+
+static torch::Tensor pc_desc_tensor(const std::vector<int64_t>& v,
+                                    const torch::Tensor& like) {
+  return torch::tensor(v, torch::kInt64).to(like.device());
+}
+
+static void launch_pc_freqs_ragged(const torch::Tensor& q,
+                                   const int64_t* desc_dev, int64_t B,
+                                   const int* items, int64_t n,
+                                   const torch::Tensor& wts, int64_t k,
+                                   int64_t L, float* logits, int* freqs,
+                                   bool portable) {
+  if (n == 0) return;
+  const int kp = (int)((k + 7) / 8 * 8);
+  auto kernel =
+      portable ? pc_freqs_ragged_kernel<true> : pc_freqs_ragged_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(PC_THREADS), 0,
+                     at::cuda::getCurrentCUDAStream(), q.data_ptr<float>(),
+                     desc_dev, (int)B, items, wts.data_ptr<float>(), (int)k,
+                     kp, (int)L, logits, freqs);
+}
+
+// (logits, tables) of every item, both (n, L), after pc_ragged_check.
+static std::tuple<torch::Tensor, torch::Tensor> pc_tables_ragged(
+    const torch::Tensor& q, const std::vector<int64_t>& desc, int64_t B,
+    const torch::Tensor& items, const torch::Tensor& wts, int64_t k,
+    int64_t L, bool portable, bool want_logits) {
+  const bool on_gpu = q.is_cuda();
+  const int64_t n = items.size(0);
+  TORCH_CHECK(n <= 0x7fffffff, "pc_codec: ", n, " items are above the 2^31-1 "
+              "one launch takes; split the batch");
+  torch::Tensor logits;
+  if (on_gpu || want_logits) logits = torch::empty({n, L}, q.options());
+  auto freqs = torch::empty({n, L}, items.options());
+  if (on_gpu) {
+    auto desc_dev = pc_desc_tensor(desc, q);
+    launch_pc_freqs_ragged(q, desc_dev.data_ptr<int64_t>(), B,
+                           items.data_ptr<int>(), n, wts, k, L,
+                           logits.data_ptr<float>(), freqs.data_ptr<int>(),
+                           portable);
+  } else {
+    const PcHostArgs a{q.data_ptr<float>(), 0, 0, items.data_ptr<int>(),
+                       pc::unpack(wts.data_ptr<float>(), (int)k, (int)L),
+                       want_logits ? logits.data_ptr<float>() : nullptr,
+                       freqs.data_ptr<int>()};
+    pc_host_eval_ragged(a, desc.data(), 0, n);
+  }
+  return {logits, freqs};
+}
+
+std::tuple<torch::Tensor, torch::Tensor> pc_freqs_ragged(
+    torch::Tensor q, std::vector<int64_t> desc, torch::Tensor items,
+    torch::Tensor wts, int64_t k, int64_t L, bool portable) {
+  int64_t total;
+  const int64_t B = pc_ragged_check(q, desc, items, wts, k, L, q.is_cuda(),
+                                    portable, &total);
+  return pc_tables_ragged(q, desc, B, items, wts, k, L, portable, true);
+}
+
+// Context model + range encoder of a ragged batch. items are sorted by
+// (b, t, c, h, w); image b owns items and syms [starts[b], starts[b+1]).
+// Returns the flat rows: image b's starts at pcb::ragged_row_offset(b,
+// starts[b]) and holds its 8-byte payload length, then 3 n_b + 16 bytes.
+// Two launches on the GPU.
+torch::Tensor pc_encode_ragged(torch::Tensor q, std::vector<int64_t> desc,
+                               torch::Tensor items,
+                               std::vector<int64_t> starts, torch::Tensor syms,
+                               torch::Tensor wts, int64_t k, int64_t L,
+                               bool portable) {
+  const bool on_gpu = q.is_cuda();
+  int64_t total;
+  const int64_t B =
+      pc_ragged_check(q, desc, items, wts, k, L, on_gpu, portable, &total);
+  pc_check_tensor(syms, "symbols", on_gpu);
+  const int64_t n = items.size(0);
+  TORCH_CHECK(syms.scalar_type() == torch::kInt32 && syms.dim() == 1 &&
+                  syms.size(0) == n,
+              "pc_encode_ragged: symbols must be int32 (n,), one per item");
+  TORCH_CHECK((int64_t)starts.size() == B + 1 &&
+                  pcb::offsets_ok(starts.data(), B, n),
+              "pc_encode_ragged: starts must be B+1 values running from 0 to "
+              "n without decreasing");
+  if (!on_gpu) {
+    const int* it = items.data_ptr<int>();
+    for (int64_t b = 0; b < B; ++b)
+      for (int64_t i = starts[b]; i < starts[b + 1]; ++i)
+        TORCH_CHECK(it[4 * i] == b, "pc_encode_ragged host: item ", i,
+                    " lies in the range of image ", b, " but names image ",
+                    it[4 * i]);
+  }
+  auto freqs = std::get<1>(
+      pc_tables_ragged(q, desc, B, items, wts, k, L, portable, false));
+  auto out = torch::zeros({pcb::ROW_EXTRA * B + 3 * n},
+                          syms.options().dtype(torch::kUInt8));
+  if (on_gpu) {
+    auto starts_dev = pc_desc_tensor(starts, q);
+    hipLaunchKernelGGL(rc_encode_ragged_kernel, dim3((unsigned)B),
+                       dim3(RC_CHUNK), 0, at::cuda::getCurrentCUDAStream(),
+                       syms.data_ptr<int>(), freqs.data_ptr<int>(),
+                       starts_dev.data_ptr<int64_t>(), (int)L,
+                       out.data_ptr<uint8_t>());
+    return out;
+  }
+  const int* sp = syms.data_ptr<int>();
+  const int* fp = freqs.data_ptr<int>();
+  uint8_t* op = out.data_ptr<uint8_t>();
+  host_parallel_for(0, B, 1, [&](int64_t lo, int64_t hi) {
+    pcb::encode_ragged(sp, fp, starts.data(), (int)L, op, lo, hi);
+  });
+  return out;
+}
+
+// Wavefront decode of a ragged batch; q is filled in place; returns the flat
+// int64 symbols, image b's at its descriptor's offset. items are sorted by
+// (t, b, c, h, w) and seg is the (T*B + 1) segment table. GPU: one state
+// init, then two launches per non-empty wave of the merged schedule on the
+// current stream, whatever B and whatever the mix, with no host
+// synchronisation: pc_freqs_ragged over the wave's items, rc_decode_wave
+// ragged with one workgroup per image. CPU: pcb::decode_ragged over the host
+// build of the model.
+torch::Tensor pc_decode_ragged(torch::Tensor q, std::vector<int64_t> desc,
+                               torch::Tensor items, std::vector<int64_t> seg,
+                               torch::Tensor wts, int64_t k, int64_t L,
+                               torch::Tensor data,
+                               std::vector<int64_t> data_offs,
+                               torch::Tensor centers, bool portable) {
+  const bool on_gpu = q.is_cuda();
+  int64_t total;
+  const int64_t B =
+      pc_ragged_check(q, desc, items, wts, k, L, on_gpu, portable, &total);
+  const int64_t n = items.size(0);
+  TORCH_CHECK(n <= 0x7fffffff, "pc_codec: ", n, " items are above the 2^31-1 "
+              "one launch takes; split the batch");
+  TORCH_CHECK(seg.size() >= 1 && (int64_t)(seg.size() - 1) % B == 0,
+              "pc_decode_ragged: the segment table must hold T*B + 1 values");
+  const int64_t T = (int64_t)(seg.size() - 1) / B;
+  TORCH_CHECK(T >= 1 && pcb::offsets_ok(seg.data(), T * B, n),
+              "pc_decode_ragged: the segment table must run from 0 to n "
+              "without decreasing");
+  // the uniform checks of data, centers and the payload offsets
+  pc_decode_check({0, n}, n, data, data_offs, B, centers, L, on_gpu);
+  auto out = torch::zeros({total}, items.options().dtype(torch::kInt64));
+  if (n == 0) return out;
+  if (!on_gpu) {
+    const int64_t i = pcb::first_misfiled_item(items.data_ptr<int>(),
+                                               seg.data(), T, B);
+    TORCH_CHECK(i == n, "pc_decode_ragged host: item ", i,
+                " lies in the segment of another image");
+    auto freqs = torch::empty({n, L}, items.options());
+    const PcHostArgs a{q.data_ptr<float>(), 0, 0, items.data_ptr<int>(),
+                       pc::unpack(wts.data_ptr<float>(), (int)k, (int)L),
+                       nullptr, freqs.data_ptr<int>()};
+    const pcb::RaggedDecodeArgs d{
+        B, T, (int)L, desc.data(), items.data_ptr<int>(), seg.data(),
+        freqs.data_ptr<int>(), data.data_ptr<uint8_t>(), data_offs.data(),
+        centers.data_ptr<float>(), q.data_ptr<float>(),
+        out.data_ptr<int64_t>()};
+    pcb::decode_ragged(d, [&](int64_t lo, int64_t hi) {
+      pc_host_eval_ragged(a, desc.data(), lo, hi);
+    });
+    return out;
+  }
+  int64_t maxw = 0;
+  for (int64_t t = 0; t < T; ++t)
+    maxw = std::max(maxw, seg[(t + 1) * B] - seg[t * B]);
+  auto logits = torch::empty({maxw, L}, q.options());
+  auto freqs = torch::empty({maxw, L}, items.options());
+  auto desc_dev = pc_desc_tensor(desc, q);
+  auto seg_dev = pc_desc_tensor(seg, q);
+  auto offs_dev = pc_desc_tensor(data_offs, q);
+  const int64_t* offs = offs_dev.data_ptr<int64_t>();
+  auto state = decode_state(data, offs, B);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const int* it = items.data_ptr<int>();
+  for (int64_t t = 0; t < T; ++t) {
+    const int64_t o = seg[t * B], nw = seg[(t + 1) * B] - o;
+    if (nw == 0) continue;
+    launch_pc_freqs_ragged(q, desc_dev.data_ptr<int64_t>(), B, it + 4 * o, nw,
+                           wts, k, L, logits.data_ptr<float>(),
+                           freqs.data_ptr<int>(), portable);
+    hipLaunchKernelGGL(rc_decode_wave_ragged_kernel, dim3((unsigned)B),
+                       dim3(RC_CHUNK), 0, stream,
+                       reinterpret_cast<rc::State*>(state.data_ptr<int64_t>()),
+                       data.data_ptr<uint8_t>(), (uint64_t)data.numel(), offs,
+                       freqs.data_ptr<int>(), it, seg_dev.data_ptr<int64_t>(),
+                       t, desc_dev.data_ptr<int64_t>(), (int)L,
+                       centers.data_ptr<float>(), q.data_ptr<float>(),
+                       out.data_ptr<int64_t>());
   }
   return out;
 }

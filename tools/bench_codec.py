@@ -4,6 +4,7 @@
                                 [--runs 5] [--warmup 1]
                                 [--shapes 32x8x12,32x40x120] [--zero-frac 0.5]
                                 [--batch 1,2,4,8,16]
+                                [--ragged 32x46x155,32x46x153,..]
 
 --device defaults to the GPU; --device cpu times the portable backend's host
 build (or the torch backend) and reports the thread count.
@@ -36,6 +37,18 @@ the launch counts computed from the wave schedule (encode 2, decode
 loop issues exactly these and a kernel trace confirms it). Every
 decode, batched and sequential, is checked against the symbols, and the
 batched streams against the sequential ones.
+
+--ragged SHAPE,SHAPE,.. times a batch of symbol volumes of different shapes
+(a shape may repeat; --shapes and --batch are ignored) three ways,
+alternately in one process: "ragged", one encode_symbols_ragged /
+decode_symbols_ragged call over all the volumes; "grouped", one
+encode_symbols_batch / decode_symbols_batch call per group of equal shapes
+(the best the uniform batch path can do); "single", one encode_symbols /
+decode_symbols call per volume. One JSON line with the three times for
+encode and for decode, the ratios against ragged, and the launch counts
+computed from the schedules (ragged decode: one state init plus two per
+non-empty wave of the merged schedule). Every run compares the three sets of
+streams byte for byte and every decode against the symbols.
 """
 
 import argparse
@@ -121,6 +134,95 @@ def bench_batch(args, dev, pc, centers, L, shape, B):
     print(json.dumps(out), flush=True)
 
 
+def bench_ragged(args, dev, pc, centers, L, shapes):
+    """One JSON line: one ragged call against one batched call per group of
+    equal shapes and against one call per volume."""
+    from dsin_amd.coding import (decode_symbols_batch, decode_symbols_ragged,
+                                 encode_symbols_batch, encode_symbols_ragged)
+    kw = {"backend": args.backend}
+    g = torch.Generator().manual_seed(1)
+    syms = []
+    for shape in shapes:
+        s = torch.randint(0, L, shape, generator=g)
+        s[torch.rand(shape, generator=g) < args.zero_frac] = 0
+        syms.append(s.to(dev))
+    groups = {}
+    for i, shape in enumerate(shapes):
+        groups.setdefault(shape, []).append(i)
+    stacked = {shape: torch.stack([syms[i] for i in idx])
+               for shape, idx in groups.items()}
+    pad = pc.context_size() // 2
+    wave_t = {shape: {25 * w[0][0] + 5 * w[0][1] + w[0][2]
+                      for w in _wave_order(*shape, pad)} for shape in groups}
+    merged = len(set().union(*wave_t.values()))
+
+    def enc_grouped():
+        out = [None] * len(shapes)
+        for shape, idx in groups.items():
+            for i, d in zip(idx, encode_symbols_batch(pc, centers,
+                                                      stacked[shape], **kw)):
+                out[i] = d
+        return out
+
+    def dec_grouped(datas):
+        out = [None] * len(shapes)
+        for shape, idx in groups.items():
+            dec = decode_symbols_batch(pc, centers, [datas[i] for i in idx],
+                                       shape, **kw)
+            for i, o in zip(idx, dec):
+                out[i] = o
+        return out
+
+    names = ("ragged", "grouped", "single")
+    t = {f"{op}_{n}": [] for op in ("encode", "decode") for n in names}
+    for it in range(args.warmup + args.runs):
+        enc = [timed(lambda: encode_symbols_ragged(pc, centers, syms, **kw),
+                     dev),
+               timed(enc_grouped, dev),
+               timed(lambda: [encode_symbols(pc, centers, s, **kw)
+                              for s in syms], dev)]
+        datas = enc[0][0]
+        if not (enc[1][0] == datas and enc[2][0] == datas):
+            sys.exit(f"bench_codec: ragged streams differ at {shapes}")
+        dec = [timed(lambda: decode_symbols_ragged(pc, centers, datas, shapes,
+                                                   **kw), dev),
+               timed(lambda: dec_grouped(datas), dev),
+               timed(lambda: [decode_symbols(pc, centers, d, sh, **kw)
+                              for d, sh in zip(datas, shapes)], dev)]
+        for outs, _ in dec:
+            if not all(torch.equal(o, s) for o, s in zip(outs, syms)):
+                sys.exit(f"bench_codec: ragged roundtrip failed at {shapes}")
+        if it >= args.warmup:
+            for n, (_, te), (_, td) in zip(names, enc, dec):
+                t[f"encode_{n}"].append(te)
+                t[f"decode_{n}"].append(td)
+    med = {k: statistics.median(v) for k, v in t.items()}
+    out = {"backend": args.backend, "device": dev.type,
+           "ragged_shapes": [list(s) for s in shapes],
+           "images": len(shapes), "size_groups": len(groups),
+           "symbols": sum(s.numel() for s in syms),
+           "zero_frac": args.zero_frac, "runs": args.runs,
+           "warmup": args.warmup, "merged_waves": merged,
+           "stream_bytes": sum(len(d) for d in datas)}
+    for k, v in t.items():
+        out[k + "_ms"] = stats(v)
+    for op in ("encode", "decode"):
+        for n in names[1:]:
+            out[f"{op}_{n}_over_ragged"] = round(
+                med[f"{op}_{n}"] / med[f"{op}_ragged"], 3)
+    if dev.type != "cuda":
+        out["threads"] = torch.get_num_threads()
+    else:
+        # from the schedules, not counted: what the C++ loops issue
+        out["encode_launches_computed"] = {
+            "ragged": 2, "grouped": 2 * len(groups), "single": 2 * len(shapes)}
+        out["decode_launches_computed"] = {
+            "ragged": 1 + 2 * merged,
+            "grouped": sum(1 + 2 * len(wave_t[s]) for s in groups),
+            "single": sum(1 + 2 * len(wave_t[s]) for s in shapes)}
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--backend", default="hip",
@@ -133,6 +235,10 @@ def main():
     ap.add_argument("--batch", default=None,
                     help="comma-separated batch sizes: time one batched call "
                          "against B sequential single-image calls")
+    ap.add_argument("--ragged", default=None,
+                    help="comma-separated CxHxW volumes of one mixed batch: "
+                         "time one ragged call against one batched call per "
+                         "size group and one call per volume")
     args = ap.parse_args()
     dev = torch.device(args.device)
     if dev.type == "cuda" and not torch.cuda.is_available():
@@ -147,6 +253,15 @@ def main():
     torch.manual_seed(0)
     pc = ProbClass(pcc, num_centers=L).to(dev).eval()
     centers = torch.linspace(-2, 2, L, device=dev)
+
+    if args.ragged:
+        if args.backend == "torch":
+            sys.exit("bench_codec: --ragged times the hip and portable "
+                     "backends (torch loops over the images)")
+        bench_ragged(args, dev, pc, centers, L,
+                     [tuple(int(s) for s in spec.split("x"))
+                      for spec in args.ragged.split(",")])
+        return
 
     for spec in args.shapes.split(","):
         shape = tuple(int(s) for s in spec.split("x"))

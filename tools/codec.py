@@ -6,6 +6,21 @@
     python tools/codec.py compress-batch   [--backend portable] --out-dir DIR <checkpoint> <a.png> <b.png> ..
     python tools/codec.py decompress-batch --out-dir DIR [--side ya.png --side yb.png ..] <checkpoint> <a.dsin> <b.dsin> ..
 
+    python tools/codec.py compress-many   [--backend portable] --out FILE.dsna <checkpoint> <a.png> <b.png> ..
+    python tools/codec.py decompress-many --out-dir DIR [--side ya.png --side yb.png ..] <checkpoint> FILE.dsna
+
+compress-many takes images of any sizes (each a multiple of 8 in both
+dimensions) and codes them in one compress_many call: one encoder pass per
+distinct size and one ragged entropy-coder call over all of them. It writes
+one archive FILE.dsna (magic DSNA, see dsin_amd/coding/bitstream.py) that
+holds an ordinary single-image stream per image together with the image's
+file name. decompress-many opens such an archive, decodes all streams in one
+decompress_many call and writes DIR/<name>.png per image (one --side per
+image, in the archive's order, or none). The model is size-agnostic apart
+from the side-information patch: with --side the patch (--patch HxW, default
+from the config) must tile every image of the archive, otherwise the tool
+exits with a message that names the image.
+
 compress-batch takes several images of one size and codes them in one
 compress_batch call (the entropy coder runs them as one batch on the GPU),
 writing DIR/<name>.dsin per image, each an ordinary single-image stream that
@@ -35,8 +50,9 @@ import numpy as np
 import torch
 
 from dsin_amd import config as config_mod
-from dsin_amd.coding import (compress, compress_batch, decompress,
-                             decompress_batch)
+from dsin_amd.coding import (compress, compress_batch, compress_many,
+                             decompress, decompress_batch, decompress_many,
+                             pack_archive, unpack_archive)
 from dsin_amd.coding.bitstream import parse_container
 from dsin_amd.data.png import read_png, write_png
 from dsin_amd.models import DSIN
@@ -134,6 +150,62 @@ def run_batch(args, device, cast) -> None:
               f"{'x_with_si' if x_si is not None else 'x_dec'}")
 
 
+def run_many(args, device, cast) -> None:
+    """Images of different sizes: one compress_many / decompress_many call,
+    one archive."""
+    if args.cmd == "compress-many":
+        xs = [load_image(p, device) for p in args.paths]
+        names = [os.path.basename(p) for p in args.paths]
+        if len(set(os.path.splitext(n)[0] for n in names)) != len(names):
+            sys.exit("inputs of one archive need different file names")
+        model = build_model(args, xs[0].shape[1], xs[0].shape[2], device)
+        with cast:
+            datas = compress_many(model, xs, backend=args.backend)
+        with open(args.out, "wb") as f:
+            f.write(pack_archive(datas, names))
+        for name, x, data in zip(names, xs, datas):
+            bpp = 8.0 * len(data) / (x.shape[1] * x.shape[2])
+            print(f"{name}: {x.shape[1]}x{x.shape[2]}, {len(data)} bytes, "
+                  f"{bpp:.4f} bpp")
+        print(f"{args.out}: {len(datas)} images, "
+              f"{os.path.getsize(args.out)} bytes")
+        return
+    with open(args.archive, "rb") as f:
+        blob = f.read()
+    try:
+        datas, names = unpack_archive(blob)
+        sizes = [tuple(8 * v for v in parse_container(d)[1][1:])
+                 for d in datas]
+    except ValueError as e:
+        sys.exit(f"{args.archive}: {e}")
+    if not datas:
+        sys.exit(f"{args.archive}: the archive holds no image")
+    names = [n or f"image{i:04d}" for i, n in enumerate(names)]
+    if args.side and len(args.side) != len(datas):
+        sys.exit(f"{len(datas)} images need {len(datas)} --side images, got "
+                 f"{len(args.side)}")
+    outs = out_paths(args.out_dir, names, ".png")
+    model = build_model(args, sizes[0][0], sizes[0][1], device)
+    ys = None
+    if args.side:
+        ph, pw = model.ae_config.y_patch_size
+        for name, (h, w) in zip(names, sizes):
+            if h % ph or w % pw:
+                sys.exit(f"{name}: the {ph}x{pw} side-information patch does "
+                         f"not tile its {h}x{w} pixels; choose --patch so "
+                         f"that it tiles every image of the archive")
+        ys = [load_image(p, device) for p in args.side]
+    try:
+        with cast:
+            res = decompress_many(model, datas, ys)
+    except ValueError as e:
+        sys.exit(f"{args.archive}: {e}")
+    for path, (h, w), (x_dec, x_si) in zip(outs, sizes, res):
+        save_image(path, x_si if x_si is not None else x_dec)
+        print(f"{path}: {h}x{w}, "
+              f"{'x_with_si' if x_si is not None else 'x_dec'}")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--ae-config", default=os.path.join(
@@ -176,13 +248,31 @@ def main() -> None:
                          "order, or not at all")
     db.add_argument("checkpoint")
     db.add_argument("paths", nargs="+", metavar="stream")
+    cm_ = sub.add_parser("compress-many",
+                         help="code images of any sizes into one archive")
+    cm_.add_argument("--backend", default=None,
+                     choices=["torch", "hip", "portable"])
+    cm_.add_argument("--out", required=True, help="the archive FILE.dsna")
+    cm_.add_argument("checkpoint")
+    cm_.add_argument("paths", nargs="+", metavar="image")
+    dm = sub.add_parser("decompress-many",
+                        help="decode every image of an archive")
+    dm.add_argument("--out-dir", required=True,
+                    help="receives one <name>.png per image")
+    dm.add_argument("--side", action="append", default=None,
+                    help="side image y.png, once per image and in the "
+                         "archive's order, or not at all")
+    dm.add_argument("checkpoint")
+    dm.add_argument("archive")
     args = ap.parse_args()
 
     device = torch.device(args.device or (
         "cuda:0" if torch.cuda.is_available() else "cpu"))
     cast = torch.autocast("cuda", dtype=torch.bfloat16, cache_enabled=False,
                           enabled=args.bf16 and device.type == "cuda")
-    if args.cmd.endswith("-batch"):
+    if args.cmd.endswith("-many"):
+        run_many(args, device, cast)
+    elif args.cmd.endswith("-batch"):
         run_batch(args, device, cast)
     elif args.cmd == "compress":
         x = load_image(args.image, device)
